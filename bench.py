@@ -1,19 +1,26 @@
 #!/usr/bin/env python
 """Headline benchmark: images/sec of the CLIPSelf distillation step (student + teacher), BASELINE.json metric.
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N>1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" = one full training iteration of the hot path on one synthetic batch already resident in HBM:
 teacher EVA02-CLIP-B-16 forward over 64x32 region crops (224^2) -> student dense forward over 64 images (224^2) ->
 RoIAlign -> cosine loss -> student backward (12 blocks) -> [bucketed RCCL all-reduce] -> AdamW, through the same
 `train_step` the training entrypoint uses.  Workload = BASELINE.json configs[1].
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints the JSON
+line (value, ms_per_step, step_tflops, config).  --dump-outputs DIR writes what the last timed step returned (the loss terms and the
+logit scale) and a fixed, seeded sample of the student's updated parameters and gradients as DIR/<name>.npy (float64 / float32, a
+few MB); the inputs are the same from run to run, so two builds can be compared output for output.
+
+With --full the JSON line also carries
   roofline      MFMA roofline of the dominant kernel (the fused W1|W2 SwiGLU GEMM of the teacher, one shape per
                 launch): algorithmic FLOPs per launch / mean launch duration, measured with HIP events recorded on
                 the launch stream inside the timed region; peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md).
   cpu_baseline  the fp32 CPU oracle (oracle/eva_ref.py, validated against the reference) timed on the host cores on a
                 bounded sample of the same workload (rank 0, N=1 only).
+  also          short runs of the other configurations (tools/also_bench.py; N=1 only).
+  data_parallel per-bucket all-reduce statistics and the design's prediction beside them (data-parallel runs only).
 """
 import argparse
 import json
@@ -323,11 +330,46 @@ def expected_data_parallel(world, cfg_blocks=12, bucket_mb=28.3, one_gpu_ms=ONE_
                        "growing from bucket to bucket: the links are the limit -> --bf16-grad-buckets halves the bytes"}
 
 
+DUMP_SAMPLE = 4096          # elements per parameter tensor in the --dump-outputs sample
+
+
+def dump_outputs(out_dir, losses, logit_scale, student):
+    """What the last timed step computed, as DIR/<name>.npy: every loss term train_step returned and the logit scale (float64), and
+    the student's updated trainable parameters and their gradients, sampled at the same seeded positions of every tensor in
+    named_parameters() order (float32; at most DUMP_SAMPLE elements per tensor)."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, v in (losses or {}).items():
+        np.save(d / f"{k}.npy", v.detach().double().reshape(-1).cpu().numpy())
+    np.save(d / "logit_scale.npy", logit_scale.detach().double().reshape(-1).cpu().numpy())
+    g = torch.Generator().manual_seed(0)
+    params, grads = [], []
+    with torch.no_grad():
+        for _, p in student.named_parameters():
+            if not p.requires_grad:
+                continue
+            n = p.numel()
+            idx = torch.arange(n) if n <= DUMP_SAMPLE else torch.randint(n, (DUMP_SAMPLE,), generator=g)
+            idx = idx.to(p.device)
+            params.append(p.detach().reshape(-1)[idx].float().cpu())
+            grads.append(torch.zeros(len(idx)) if p.grad is None else p.grad.detach().reshape(-1)[idx].float().cpu())
+    np.save(d / "student_params_sample.npy", torch.cat(params).numpy())
+    np.save(d / "student_grads_sample.npy", torch.cat(grads).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure and check everything else: the dominant kernel's roofline (HIP events inside the "
+                         "timed region, the isolated launch, live PMC traffic), the other configurations (`also`), the CPU baseline and the "
+                         "data-parallel diagnostics.  Off by default: a plain run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (loss terms, logit scale, a seeded "
+                         "sample of the student's updated parameters and gradients)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="report roofline.traffic from the tracked PMC summary (profiles/pmc_traffic.json) instead of two rocprofv3 counter passes "
@@ -433,7 +475,7 @@ def main():
     args.teacher_prefetch = not a.no_overlap
     method = CLIPSelf()
     # the fused SwiGLU GEMM is launched by the teacher's engine; the full-token launches (M = chunk*197) are the dominant kernel
-    timer = KernelTimer(teacher.visual.engine.ops, epi=3, min_rows=min(a.teacher_chunk, BATCH * CROPS) * cfg.tokens)
+    timer = KernelTimer(teacher.visual.engine.ops, epi=3, min_rows=min(a.teacher_chunk, BATCH * CROPS) * cfg.tokens) if a.full else None
 
     def sync():
         if distributed:
@@ -445,19 +487,21 @@ def main():
         train_step(model, method, batches[step % 2], opt, sched, step, dist_model, args, next_batch=batches[(step + 1) % 2])
         step += 1
     sync()
-    if distributed:
+    if distributed and a.full:
         model.collect_stats(True)               # per-bucket issue -> completion events and the exposed wait, for the timed steps only
-    timer.on = True
+    if timer is not None:
+        timer.on = True
     t0 = time.perf_counter()
-    last = None
+    last, logit_scale = None, None
     for _ in range(a.steps):
-        last, _, _ = train_step(model, method, batches[step % 2], opt, sched, step, dist_model, args, next_batch=batches[(step + 1) % 2])
+        last, _, logit_scale = train_step(model, method, batches[step % 2], opt, sched, step, dist_model, args, next_batch=batches[(step + 1) % 2])
         step += 1
     sync()
     elapsed = time.perf_counter() - t0
-    timer.on = False
+    if timer is not None:
+        timer.on = False
     comm = None
-    if distributed:
+    if distributed and a.full:
         # what the step exchanged and how long AdamW stood behind it (max over ranks), and how many ranks the collective really spans
         comm = model.comm_summary()
         t = torch.tensor([elapsed, comm["grad_sync_wait_ms"]], device=device, dtype=torch.float64)
@@ -466,15 +510,21 @@ def main():
         ones = torch.ones(1, device=device)
         dist.all_reduce(ones)
         comm["ranks_seen"] = int(ones.item())
+    elif distributed:
+        t = torch.tensor([elapsed], device=device, dtype=torch.float64)      # the slowest rank's time
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t[0])
     loss = last["loss"].detach().item() if last is not None else float("nan")
+    if a.dump_outputs and rank == 0 and a.steps > 0:
+        dump_outputs(a.dump_outputs, last, logit_scale, student)
 
     if rank == 0:
         ips = world * BATCH * a.steps / elapsed
         F = flops_per_image(cfg, CROPS, cls_only=not a.full_last_block)
-        kt = timer.result()
-        traffic, pmc = pmc_traffic_per_launch(min(a.teacher_chunk, BATCH * CROPS))
-        if world == 1 and not a.no_live_traffic and not a.no_cpu_baseline and os.environ.get("CLIPSELF_BENCH_NO_PMC") != "1":
-            # the default bench run re-measures the figure (after the timed region; ~40 s); the tracked constant stays as the fallback
+        kt = timer.result() if timer is not None else None
+        traffic, pmc = pmc_traffic_per_launch(min(a.teacher_chunk, BATCH * CROPS)) if a.full else (None, None)
+        if a.full and world == 1 and not a.no_live_traffic and not a.no_cpu_baseline and os.environ.get("CLIPSELF_BENCH_NO_PMC") != "1":
+            # a --full run re-measures the figure (after the timed region; ~40 s); the tracked constant stays as the fallback
             torch.cuda.synchronize()
             live, rec = measure_traffic_live(min(a.teacher_chunk, BATCH * CROPS))
             if live is not None:
@@ -511,7 +561,7 @@ def main():
             # xGMI link), buckets, the exposed wait in front of AdamW, CUs the persistent GEMMs leave to RCCL's kernels
             out["data_parallel"] = comm
             out["data_parallel"]["expected"] = expected_data_parallel(world, cfg_blocks=cfg.layers)
-        if world == 1 and not a.no_also and not a.no_cpu_baseline and os.environ.get("CLIPSELF_BENCH_NO_ALSO") != "1":      # (quick --no-cpu-baseline runs skip it, like the PMC passes)
+        if a.full and world == 1 and not a.no_also and not a.no_cpu_baseline and os.environ.get("CLIPSELF_BENCH_NO_ALSO") != "1":      # (quick --no-cpu-baseline runs skip it, like the PMC passes)
             # free this process's towers and activations first: the other workloads get the device to themselves
             del timer, model, dist_model, student, teacher, opt, batches, method, last
             import gc
@@ -519,7 +569,7 @@ def main():
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
             out["also"] = also_workloads(a.also_steps)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if distributed:

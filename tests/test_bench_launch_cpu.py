@@ -63,3 +63,30 @@ def test_floor_table_reproduces_from_the_tracked_launch_sequence():
     assert 70.0 < floor < measured < 95.0
     tracked = (ROOT / "profiles" / "r06_floor.md").read_text()
     assert f"**{floor:.2f}**" in tracked and f"**{measured:.2f}**" in tracked
+
+
+def test_dump_outputs_writes_the_step_results_at_fixed_sample_positions(tmp_path):
+    """bench.py --dump-outputs on a stand-in model (CPU): every loss term and the logit scale as float64, the trainable parameters and
+    their gradients sampled at the same seeded positions on every call (float32), frozen parameters left out."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(100, 80), torch.nn.Linear(80, 3))
+    m[1].bias.requires_grad_(False)
+    m(torch.randn(4, 100)).sum().backward()
+    losses = {"loss_cosine": torch.tensor(0.25), "loss": torch.tensor(0.25)}
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, losses, torch.tensor(100.0), m)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    assert sorted(a) == ["logit_scale.npy", "loss.npy", "loss_cosine.npy", "student_grads_sample.npy", "student_params_sample.npy"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["loss.npy"].dtype == np.float64 and a["logit_scale.npy"][0] == 100.0
+    n = bench.DUMP_SAMPLE + 80 + 80 * 3                      # W1 (8000 elements) sampled; b1, W2 whole; b2 frozen
+    p, g = a["student_params_sample.npy"], a["student_grads_sample.npy"]
+    assert p.dtype == g.dtype == np.float32 and p.shape == g.shape == (n,)
+    assert np.isin(p[:bench.DUMP_SAMPLE], m[0].weight.detach().numpy().ravel()).all()
+    assert np.array_equal(p[bench.DUMP_SAMPLE:], torch.cat([m[0].bias.detach(), m[1].weight.detach().ravel()]).numpy())
+    assert np.array_equal(g[bench.DUMP_SAMPLE:], torch.cat([m[0].bias.grad, m[1].weight.grad.ravel()]).numpy())

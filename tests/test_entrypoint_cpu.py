@@ -29,6 +29,7 @@ def tiny_model_config(monkeypatch):
     import clipself_amd.open_clip.model as model
     monkeypatch.setattr(model, "_default_ops", lambda: RefOps())
     monkeypatch.setattr(hip, "HipOps", RefOps)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)     # the reference ops compute on the host: main() picks the CPU on a GPU box too
     yield "EVA02-tiny-entry"
     path.unlink()
     for h in list(logging.root.handlers):                      # main() installs console / file handlers bound to this test's streams

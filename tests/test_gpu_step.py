@@ -324,7 +324,7 @@ def test_bench_rccl_single_rank_path():
     for force in ("1", "0"):
         env = dict(os.environ, CLIPSELF_FORCE_DIST=force, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
         env.pop("WORLD_SIZE", None)
-        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-overlap"],
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-overlap"],
                            cwd=root, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         outs.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))

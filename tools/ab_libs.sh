@@ -12,7 +12,7 @@ done
 for r in 0 1; do
   for lib in $A $B; do
     echo "# $lib" >> $out/bench_ab.jsonl
-    CLIPSELF_HIP_LIB=$lib python bench.py --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | grep '^{' >> $out/bench_ab.jsonl
+    CLIPSELF_HIP_LIB=$lib python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | grep '^{' >> $out/bench_ab.jsonl
   done
 done
 cat $out/gemm_ab.txt
