@@ -16,9 +16,7 @@
 //   * keys are consumed in chunks of CH*32 with an online softmax, so any sequence length works; for the
 //     14x14(+CLS) grid a single chunk of 224 covers all 197 keys and no rescale is ever taken.
 #include <type_traits>
-#include <vector>
 #include "cs_common.h"
-#include <cstdio>
 #include <cstdlib>
 
 namespace {
@@ -65,33 +63,8 @@ __device__ __forceinline__ void rope8_lds(U128& v, const float* rt, int g, float
     const float* cs = rt + ((c8 < 4 ? r : 2 * g + c) << 5) + (c8 & 3) * 8;
     rope8(v, cs, cs + (g << 5));
 }
-
-// Round 6: the tables ONCE per frequency.  rope.py:118-142 builds the row part and the column part from the same `freqs` tensor and repeats
-// every frequency for the two dims of a pair: cos_row[r][2j] == cos_row[r][2j+1] == cos_col[r][2j].  rt = cos [g][16] | sin [g][16] (a quarter of
-// the [4][g][32] tables above: 8 KB instead of 32 KB at the recipe's 64 x 64 grid); same products, same bits as rope8_lds.  A documented
-// precondition of the C ABI (include/clipself_hip.h), verified by HipOps once per table tensor.
-__device__ __forceinline__ void rope8c(U128& v, const float* rt, int g, float inv_g, int tok, int c8) {
-    const int t = tok - 1;
-    const int r = (int)(((float)t + 0.5f) * inv_g), c = t - r * g;
-    const float* cs = rt + ((c8 < 4 ? r : c) << 4) + (c8 & 3) * 4;
-    const float4 c4 = *(const float4*)cs, s4 = *(const float4*)(cs + (g << 4));
-    const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {              // the written-out contraction of rope8
-        const float x0 = bf2f(v.e[2 * j]), x1 = bf2f(v.e[2 * j + 1]);
-        v.e[2 * j] = f2bf(__builtin_fmaf(x0, cc[j], -(x1 * ss[j])));
-        v.e[2 * j + 1] = f2bf(__builtin_fmaf(x1, cc[j], x0 * ss[j]));
-    }
-}
-
-template <int NT>
-__device__ __forceinline__ void load_rope_tables_c(float* rt, const float* __restrict__ cos_t, const float* __restrict__ sin_t, int g, int tid) {
-    for (int i = tid; i < g * 16; i += NT) {               // the column part of grid row 0: token i >> 4, dims 32 + 2 (i & 15)
-        const int r = i >> 4, j = i & 15;
-        rt[i] = cos_t[(size_t)r * HD + 32 + 2 * j];
-        rt[(g << 4) + i] = sin_t[(size_t)r * HD + 32 + 2 * j];
-    }
-}
+// (Tried and removed, round 6: tables stored ONCE per frequency, cos [g][16] | sin [g][16], for a three-units-per-CU forward that tied with
+// attn_fwd8_kernel.  profiles/r06_c_attention_pipes.md)
 
 template <int NT>
 __device__ __forceinline__ void load_rope_tables(float* rt, const float* __restrict__ cos_t, const float* __restrict__ sin_t, int g, int tid) {
@@ -148,15 +121,7 @@ struct AttnArgs {
     int sch_on, sch_f0, sch_r, sch_bh, sch_fb, sch_rem, sch_absorb;
     const __bf16* qk;      // PRE kernels: rotated q | k, [B*N, ldqk] (rope_qk_kernel)
     int ldqk;
-#ifdef CS_ABLATION_SWITCHES
-    unsigned long long* trace;   // env CS_ATTN_TRACE=<file>: per workgroup 8 x u64 (HW_ID, XCC_ID, 100 MHz clock at entry / tables / images / attended / end)
-#endif
 };
-#ifdef CS_ABLATION_SWITCHES
-#define ATT_TRACE(slot) do { if (p.trace && threadIdx.x == 0) p.trace[(size_t)blockIdx.y * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define ATT_TRACE(slot) do { } while (0)
-#endif
 
 // Round 6: the tail of a launch is split.  The long-sequence kernels run ONE 8-wave workgroup per CU (216-247 VGPRs), a workgroup = 8 row tiles of 32
 // (256 queries resp. keys) of one (image, head) against the whole sequence.  At the recipe's 2 x 12 x 4097 that is 16 x 24 = 384 equal workgroups
@@ -222,48 +187,6 @@ constexpr int VT_LD = 264;            // 33 blocks of 8 keys: odd block stride -
 
 __device__ __forceinline__ int k_off(int r, int c) { return ((r >> 1) << 8) + (((((r & 1) << 3) | c) ^ ((r >> 1) & 15)) << 4); }
 
-template <int CHK, int NT>
-__device__ __forceinline__ void stage_k(const __bf16* __restrict__ src, size_t rowbase, int ld, int coloff, int tok0, int Ntok,
-                                        const float* rt, int g, float inv_g, char* tile, int tid) {
-    constexpr int ITEMS = (CHK * 8 + NT - 1) / NT;
-    U128 v[ITEMS];
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {                      // all loads in flight before the first use
-        const int idx = min(tid + it * NT, CHK * 8 - 1), tok = min(tok0 + (idx >> 3), Ntok - 1);   // branch-free: padding rows repeat the last row
-        v[it].u = *(const uint4*)(src + (rowbase + tok) * ld + coloff + (idx & 7) * 8);
-    }
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int idx = tid + it * NT, r = idx >> 3, c = idx & 7, tok = tok0 + r;
-        if (idx < CHK * 8) {
-            if (tok > 0 && tok < Ntok) rope8_lds(v[it], rt, g, inv_g, tok, c);
-            *(uint4*)(tile + k_off(r, c)) = v[it].u;
-        }
-    }
-}
-
-template <int CHK, int NT>
-__device__ __forceinline__ void stage_vt(const __bf16* __restrict__ src, size_t rowbase, int ld, int coloff, int tok0, int Ntok,
-                                         __bf16* vt, int tid) {
-    for (int idx = tid; idx < CHK; idx += NT) {              // CHK/8 key blocks x 8 dim chunks
-        const int kb = idx >> 3, c = idx & 7;
-        U128 in[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int tok = min(tok0 + kb * 8 + i, Ntok - 1);        // branch-free (see attn_fwd_kernel): padding keys carry p = 0
-            in[i].u = *(const uint4*)(src + (rowbase + tok) * ld + coloff + c * 8);
-        }
-        const int pos = (kb ^ c) * 8;                        // (d>>3)&7 == c for d = c*8 + j
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            U128 o;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o.e[i] = in[i].e[j];
-            *(uint4*)(vt + (c * 8 + j) * VT_LD + pos) = o.u;
-        }
-    }
-}
-
 // ---- round 5: row-major images + transposing reads (attention backward, long-sequence forward) -------------------------------------
 typedef short s16x4v __attribute__((ext_vector_type(4)));
 
@@ -299,8 +222,7 @@ struct RowRegs {
     }
     // ZPAD: rows past the sequence are stored as zeros (the dQ kernel: a zero K row contributes nothing to dQ^T += K^T . dS^T whatever its
     // dS column holds, so the hot loop masks nothing)
-    // CT: rt holds the compact tables (one entry per frequency, rope8c)
-    template <bool ROPE, bool ZPAD = false, bool CT = false>
+    template <bool ROPE, bool ZPAD = false>
     __device__ __forceinline__ void store(char* tile, const float* rt, int g, float inv_g, int tok0, int Ntok, int tid) {
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
@@ -308,10 +230,7 @@ struct RowRegs {
             if (idx < CHK * 8) {
                 U128 t;
                 t.u = v[it];
-                if (ROPE && tok > 0 && tok < Ntok) {
-                    if constexpr (CT) rope8c(t, rt, g, inv_g, tok, c);
-                    else rope8_lds(t, rt, g, inv_g, tok, c);
-                }
+                if (ROPE && tok > 0 && tok < Ntok) rope8_lds(t, rt, g, inv_g, tok, c);
                 if (ZPAD && tok >= Ntok) t.u = make_uint4(0, 0, 0, 0);
                 *(uint4*)(tile + k_off(r, c)) = t.u;
             }
@@ -335,17 +254,13 @@ __device__ __forceinline__ bf16x8 pack8_swapped(const f32x16& a, int c2) {
     return out.v;
 }
 
-template <bool CT = false>
 __device__ __forceinline__ void load_q_frags(const AttnArgs& p, const float* rt, size_t rowbase, int qc, int h, int hf, bf16x8 (&qf)[4]) {
     U128 t[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) t[ks].u = *(const uint4*)(p.qkv + (rowbase + qc) * p.ldqkv + h * HD + ks * 16 + hf * 8);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        if (qc > 0) {
-            if constexpr (CT) rope8c(t[ks], rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
-            else rope8_lds(t[ks], rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
-        }
+        if (qc > 0) rope8_lds(t[ks], rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
         qf[ks] = t[ks].h;
     }
 }
@@ -353,25 +268,18 @@ __device__ __forceinline__ void load_q_frags(const AttnArgs& p, const float* rt,
 // one key chunk against one 32-query tile: S^T = K Q^T, online-softmax update of (m, l), O^T += V^T P^T
 // t0: first key tile of the chunk inside the LDS images (0 when the images hold only this chunk; the V^T key-block swizzle is a function of
 // the absolute block index, so a chunk of a whole-sequence image cannot be addressed through an offset pointer)
-// VROW: Vt points at a ROW-MAJOR [keys][64] image in the k_off layout instead of the transposed one; the V^T fragments are then read with
-// ds_read_b64_tr_b16 (half hf supplies keys 8 hf .. 8 hf + 7 of the 16-key step, the conventional order pack8_swapped produces).
-// VM, the V image (round 6):
-//   0  V^T [64][264], key blocks XOR-permuted (rounds 1-5).  Under ds_read_b128's lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31} per wave
-//      half: MI355X_MICROARCH.md "LDS") its fragment reads are 2-WAY bank-conflicted -- 8 instead of 4 LDS cycles each, and V^T reads are two
-//      thirds of the attend phase's LDS reads (SQ_LDS_BANK_CONFLICT = 33 % of SQ_LDS_IDX_ACTIVE in profiles/r05_e_pmc_attention_lds.md)
-//   1  row-major [keys][64] in the k_off layout, fragments through ds_read_b64_tr_b16 (VROW)
-//   3  V^T [64][200] for sequences of <= 200 keys (attn_fwd4_kernel): key block kb of dim row d sits at block (kb + (d >> 5)) mod 25 -- a ROTATION
-//      instead of the XOR: conflict-free fragment reads, 4-way conflicts on the 8 transposing writes per thread and unit (tools/lds_bank_model.py)
-//   (2 was a [64][224] image rotated by the dim chunk, (kb + (d >> 3 & 7)) mod 28: conflict-free reads AND writes in attn_fwd8_kernel -- built,
-//   bit-identical, `SQ_LDS_BANK_CONFLICT` 19.9 M -> 12 M per launch, and 1 % SLOWER (425-427 vs 419-422 us per 1024-crop launch: the wrap of the
-//   rotation costs a compare + subtract per fragment address and the LDS array was 34 % busy to begin with); removed.  profiles/r06_c_attention_pipes.md)
-// The same values reach the same MFMAs in every mode: bit-identical outputs.
-constexpr int VT4_LD = 200;
-
-template <int CH, bool TAIL, int VM = 0>
+// The V image:
+//   !VROW  V^T [64][264], key blocks XOR-permuted (attn_fwd8_kernel).  Under ds_read_b128's lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}
+//          per wave half: MI355X_MICROARCH.md "LDS") its fragment reads are 2-WAY bank-conflicted -- 8 instead of 4 LDS cycles each, and V^T reads
+//          are two thirds of the attend phase's LDS reads (SQ_LDS_BANK_CONFLICT = 33 % of SQ_LDS_IDX_ACTIVE in profiles/r05_e_pmc_attention_lds.md)
+//   VROW   Vt points at a ROW-MAJOR [keys][64] image in the k_off layout (attn_fwd2_kernel); the V^T fragments are read with ds_read_b64_tr_b16
+//          (half hf supplies keys 8 hf .. 8 hf + 7 of the 16-key step, the conventional order pack8_swapped produces).
+// The same values reach the same MFMAs in both modes: bit-identical outputs.
+// (Tried and removed, round 6: V^T images with the key blocks ROTATED instead of XOR-permuted -- [64][224] rotated by the dim chunk in
+// attn_fwd8_kernel, 1 % slower; [64][200] for the four-wave forward, a tie.  profiles/r06_c_attention_pipes.md)
+template <int CH, bool TAIL, bool VROW = false>
 __device__ __forceinline__ void attend_chunk(const char* Kl, const __bf16* Vt, const bf16x8 (&qf)[4], int key0, int Ntok, float sl2,
                                              int lane, bool first, float& m, float& l, f32x16 (&o)[2], int t0 = 0) {
-    constexpr bool VROW = VM == 1;
     const int hf = lane >> 5, l31 = lane & 31;
     // fragment addressing (row = t*32 + l31): LDS row (row>>1), slot ((row&1)*8 | chunk) ^ ((row>>1)&15)
     const int k_base = (l31 >> 1) << 8, par8 = (l31 & 1) << 3, sw = l31 >> 1;
@@ -455,11 +363,6 @@ __device__ __forceinline__ void attend_chunk(const char* Kl, const __bf16* Vt, c
                 if constexpr (VROW) {
                     const char* Vl = (const char*)Vt + (t0 + t) * (16 * 256);
                     vfrag = tr_join2(tr_read4(Vl + tr_lane_off(c2 * 16 + 8 * hf, dt * 32, lane)), tr_read4(Vl + tr_lane_off(c2 * 16 + 8 * hf + 4, dt * 32, lane)));
-                } else if constexpr (VM == 3) {
-                    const int d = dt * 32 + l31;
-                    int pos = kb + dt;
-                    if ((t0 + t) * 4 + c2 * 2 + 2 >= 25) pos = pos >= 25 ? pos - 25 : pos;        // (compile-time condition: the last key tiles) blocks 25..27 = keys >= 200, p = 0: they wrap onto real, finite data
-                    vfrag = *(const bf16x8*)(Vt + d * VT4_LD + (pos << 3));
                 } else {
                     const int d = dt * 32 + l31;
                     vfrag = *(const bf16x8*)(Vt + d * VT_LD + ((kb ^ ((d >> 3) & 7)) << 3));
@@ -505,45 +408,13 @@ __device__ __forceinline__ void store_o(const AttnArgs& p, size_t rowbase, int q
     }
 }
 
-// Sequences longer than one LDS image (Ntok > 224): eight waves, one 32-query tile per wave, 256 queries per workgroup; the keys are staged
-// chunk by chunk (CH*32 keys) and consumed with the online softmax.
-template <int CH>
-__global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p) {
-    constexpr int CHK = CH * 32, NT = 512;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Kl = smem;
-    __bf16* Vt = (__bf16*)(smem + CHK * 128);
-    float* rt = (float*)(smem + CHK * 128 + HD * VT_LD * 2);      // compact RoPE tables [4][g][32]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5, l31 = lane & 31;
-    const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-    const int C = p.H * HD;
-    const size_t rowbase = (size_t)b * p.Ntok;
-    const float sl2 = p.scale * LOG2E;
-    const int q0 = blockIdx.x * 256 + wave * 32, q = q0 + l31, qc = min(q, p.Ntok - 1);
-    const bool active = q0 < p.Ntok;
-    load_rope_tables<NT>(rt, p.cos_t, p.sin_t, p.grid, tid);
-    __syncthreads();
-    bf16x8 qf[4];
-    load_q_frags(p, rt, rowbase, qc, h, hf, qf);
-    float m = -INFINITY, l = 0.f;
-    f32x16 o[2] = {zero16(), zero16()};
-    for (int key0 = 0; key0 < p.Ntok; key0 += CHK) {
-        __syncthreads();
-        stage_k<CHK, NT>(p.qkv, rowbase, p.ldqkv, C + h * HD, key0, p.Ntok, rt, p.grid, p.inv_grid, Kl, tid);
-        stage_vt<CHK, NT>(p.qkv, rowbase, p.ldqkv, 2 * C + h * HD, key0, p.Ntok, Vt, tid);
-        __syncthreads();
-        if (active) attend_chunk<CH, false>(Kl, Vt, qf, key0, p.Ntok, sl2, lane, key0 == 0, m, l, o);
-    }
-    if (active && q < p.Ntok) store_o(p, rowbase, q, h, bh, hf, m, l, o);
-}
-
-// Round 5, sequences longer than one LDS image.  attn_fwd_kernel above stages a chunk (K rotated, V transposed in registers: 8 rows per
-// thread on 224 of the 512 threads) and only then attends it -- two barriers and a full memory round trip per chunk with nothing
-// overlapping them: 234 us per block at the recipe's 4097 tokens (0.18 of the MFMA peak).  Here the NEXT chunk's K and V rows are
-// requested before the current chunk is attended (register prefetch, 4 + 4 x 16 bytes per thread), V stays row-major in LDS and its
-// transposed fragments come from ds_read_b64_tr_b16, and a staged chunk of CH tiles is attended as two online-softmax steps of CH1 and
-// CH - CH1 tiles so that the score registers (16 per tile) leave room for the prefetch.
+// Round 5, sequences longer than one LDS image (Ntok > 224): eight waves, one 32-query tile per wave, 256 queries per workgroup; the keys are
+// staged chunk by chunk (CH*32 keys) and consumed with the online softmax.  The NEXT chunk's K and V rows are requested before the current
+// chunk is attended (register prefetch, 4 + 4 x 16 bytes per thread), V stays row-major in LDS and its transposed fragments come from
+// ds_read_b64_tr_b16, and a staged chunk of CH tiles is attended as two online-softmax steps of CH1 and CH - CH1 tiles so that the score
+// registers (16 per tile) leave room for the prefetch.
+// (Tried and removed: round 1's synchronous attn_fwd_kernel -- stage a chunk, barrier, attend it -- 219-248 vs 202-206 us at the recipe's
+// 4097 tokens.  profiles/r05_c_attention_restaged_bench.txt)
 template <int CH, int CH1>
 __global__ __launch_bounds__(512, 2) void attn_fwd2_kernel(AttnArgs p) {
     constexpr int CHK = CH * 32;
@@ -579,9 +450,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd2_kernel(AttnArgs p) {
             vr.load(p.qkv, rowbase, p.ldqkv, 2 * C + h * HD, key0 + CHK, p.Ntok, tid);
         }
         if (!active) continue;
-        attend_chunk<CH1, false, 1>(Kl, (const __bf16*)Vl, qf, key0, p.Ntok, sl2, lane, key0 == 0, m, l, o, 0);
+        attend_chunk<CH1, false, true>(Kl, (const __bf16*)Vl, qf, key0, p.Ntok, sl2, lane, key0 == 0, m, l, o, 0);
         if (key0 + CH1 * 32 < p.Ntok)                     // (wave-uniform) the second step holds at least one real key
-            attend_chunk<CH - CH1, false, 1>(Kl, (const __bf16*)Vl, qf, key0 + CH1 * 32, p.Ntok, sl2, lane, false, m, l, o, CH1);
+            attend_chunk<CH - CH1, false, true>(Kl, (const __bf16*)Vl, qf, key0 + CH1 * 32, p.Ntok, sl2, lane, false, m, l, o, CH1);
     }
     if (active && q < p.Ntok) store_o(p, rowbase, q, h, bh, hf, m, l, o);
 }
@@ -597,37 +468,22 @@ __global__ __launch_bounds__(512, 2) void attn_fwd2_kernel(AttnArgs p) {
 // exp -> P.V per tile; global loads -> LDS images -> barrier per unit), not by MFMA or VALU throughput: twice the waves per SIMD is
 // what hides them.  Same arithmetic per element as the single-chunk form except that the running maximum of the first chunks rescales
 // the output accumulators (exact when the maximum does not change, one fp32 rounding of alpha * o otherwise).
-// VROW (round 5, CS_ATTN_FWD8_VROW=1; NOT the default -- measured 2 % slower): V stays row-major in LDS (staged like K, four 16-byte items per
-// thread on all 512 threads) and its transposed fragments come from ds_read_b64_tr_b16 -- no 8 x 8 in-register transposes on 224 of the 512
-// threads, 16 instead of 32 staging registers; same values into the same MFMAs: bit-identical outputs.
-// VM: the V image, see attend_chunk -- 0: the XOR-permuted V^T [64][264]; 1: row-major + transposing reads.
-template <bool TAIL, int VM>
+// (Tried and removed: round 5's V row-major in LDS + ds_read_b64_tr_b16 fragments -- bit-identical, 2 % slower per 2048-crop launch,
+// profiles/r05_h_fwd8_row_major_v.txt; round 6's four waves per unit and three units per CU -- bit-identical, a tie,
+// 424-426 vs 419-422 us per 1024-crop launch, profiles/r06_c_attention_pipes.md.)
+template <bool TAIL>
 __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
     constexpr int CH = 7, CHK = CH * 32, NT = 512;
-    constexpr bool VROW = VM == 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kl = smem;
     __bf16* Vt = (__bf16*)(smem + CHK * 128);
-    float* rt = (float*)(smem + CHK * 128 + (VROW ? CHK * 128 : HD * VT_LD * 2));      // compact RoPE tables [4][g][32]
+    float* rt = (float*)(smem + CHK * 128 + HD * VT_LD * 2);      // compact RoPE tables [4][g][32]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5, l31 = lane & 31;
     const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
     const int C = p.H * HD;
     const size_t rowbase = (size_t)b * p.Ntok;
     const float sl2 = p.scale * LOG2E;
     const int last = p.Ntok - 1;
-#ifdef CS_ABLATION_SWITCHES
-    {   // timeline experiments (profiles/r04_t_attention_timeline.md): a subset of the first residents starts (dbg >> 8) x ~4.3 us late
-        // (64: odd ids, 128: every second CU, else ids 256..511); CS_ATTN_TRACE: where and when every workgroup ran
-        const int n = (p.dbg >> 8) & 0xff, id = blockIdx.y;
-        const bool late = (p.dbg & 64) ? (id & 1) && id < 512 : (p.dbg & 128) ? ((id >> 3) & 1) && id < 512 : id >= 256 && id < 512;
-        if (n && late) for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
-        if (p.trace && threadIdx.x == 0) {
-            p.trace[(size_t)id * 8 + 0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_ID
-            p.trace[(size_t)id * 8 + 1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);     // XCC_ID
-        }
-    }
-#endif
-    ATT_TRACE(2);
     // every global load of the workgroup ahead of the first dependent instruction: tables (oldest: vmcnt retires in order), K, V, Q
     float tab[4];
     {
@@ -639,25 +495,19 @@ __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
     }
     __builtin_amdgcn_sched_barrier(0);
     constexpr int KI = (CHK * 8 + NT - 1) / NT;
-    U128 kr[VROW ? 1 : KI], vin[VROW ? 1 : 8], qraw[4];
-    RowRegs<CHK> krow, vrow;               // VROW: K and V rows as plain vectors, staged by the same routine as the backward's images
+    U128 kr[KI], vin[8], qraw[4];
     const __bf16* kbase = p.qkv + C + h * HD;
     const __bf16* vbase = p.qkv + 2 * C + h * HD;
     const int vkb = min(tid, CHK - 1) >> 3, vc = tid & 7;      // one (key block, dim chunk) item per thread, threads >= 224 repeat the last
-    if constexpr (VROW) {
-        krow.load(p.qkv, rowbase, p.ldqkv, C + h * HD, 0, p.Ntok, tid);
-        vrow.load(p.qkv, rowbase, p.ldqkv, 2 * C + h * HD, 0, p.Ntok, tid);
-    } else {
 #pragma unroll
-        for (int it = 0; it < KI; ++it) {      // branch-free: rows past the sequence re-read its last row (masked to p = 0 exactly)
-            const int idx = min(tid + it * NT, CHK * 8 - 1), tok = min(idx >> 3, last);
-            kr[it].u = *(const uint4*)(kbase + (rowbase + tok) * p.ldqkv + (idx & 7) * 8);
-        }
+    for (int it = 0; it < KI; ++it) {          // branch-free: rows past the sequence re-read its last row (masked to p = 0 exactly)
+        const int idx = min(tid + it * NT, CHK * 8 - 1), tok = min(idx >> 3, last);
+        kr[it].u = *(const uint4*)(kbase + (rowbase + tok) * p.ldqkv + (idx & 7) * 8);
+    }
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int tok = min(vkb * 8 + i, last);
-            vin[i].u = *(const uint4*)(vbase + (rowbase + tok) * p.ldqkv + vc * 8);
-        }
+    for (int i = 0; i < 8; ++i) {
+        const int tok = min(vkb * 8 + i, last);
+        vin[i].u = *(const uint4*)(vbase + (rowbase + tok) * p.ldqkv + vc * 8);
     }
     const int q0 = wave * 32, q = q0 + l31, qc = min(q, last);
 #pragma unroll
@@ -669,32 +519,25 @@ __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
         rt[(3 * p.grid << 5) + tid] = tab[3];
     }
     __syncthreads();
-    ATT_TRACE(3);
-    if constexpr (VROW) {
-        krow.template store<true>(Kl, rt, p.grid, p.inv_grid, 0, p.Ntok, tid);
-        vrow.template store<false>((char*)Vt, rt, p.grid, p.inv_grid, 0, p.Ntok, tid);
-    } else {
 #pragma unroll
-        for (int it = 0; it < KI; ++it) {      // K: rotate + swizzled LDS image
-            const int idx = tid + it * NT, r = idx >> 3, c = idx & 7;
-            if (idx < CHK * 8) {
-                if (r > 0 && r < p.Ntok && !ATT_ABL(p, 2)) rope8_lds(kr[it], rt, p.grid, p.inv_grid, r, c);
-                *(uint4*)(Kl + k_off(r, c)) = kr[it].u;
-            }
+    for (int it = 0; it < KI; ++it) {          // K: rotate + swizzled LDS image
+        const int idx = tid + it * NT, r = idx >> 3, c = idx & 7;
+        if (idx < CHK * 8) {
+            if (r > 0 && r < p.Ntok && !ATT_ABL(p, 2)) rope8_lds(kr[it], rt, p.grid, p.inv_grid, r, c);
+            *(uint4*)(Kl + k_off(r, c)) = kr[it].u;
         }
-        if (tid < CHK) {                   // V: 8x8 in-register transpose -> V^T image
-            const int pos = (vkb ^ vc) * 8;
+    }
+    if (tid < CHK) {                           // V: 8x8 in-register transpose -> V^T image
+        const int pos = (vkb ^ vc) * 8;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                U128 o;
+        for (int j = 0; j < 8; ++j) {
+            U128 o;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) o.e[i] = vin[i].e[j];
-                *(uint4*)(Vt + (vc * 8 + j) * VT_LD + pos) = o.u;
-            }
+            for (int i = 0; i < 8; ++i) o.e[i] = vin[i].e[j];
+            *(uint4*)(Vt + (vc * 8 + j) * VT_LD + pos) = o.u;
         }
     }
     __syncthreads();
-    ATT_TRACE(4);
     if (q0 >= p.Ntok) return;
     bf16x8 qf[4];
 #pragma unroll
@@ -706,132 +549,15 @@ __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
     f32x16 o[2] = {zero16(), zero16()};
     if (ATT_ABL(p, 1)) { l = 1.f; m = 0.f; o[0][0] = bf2f(qf[0][0]); }
     else if (TAIL) {                       // 192 < Ntok <= 224 (the 14x14 + CLS grid): two full chunks and the ragged last tile
-        attend_chunk<3, false, VM>(Kl, Vt, qf, 0, p.Ntok, sl2, lane, true, m, l, o, 0);
-        attend_chunk<3, false, VM>(Kl, Vt, qf, 96, p.Ntok, sl2, lane, false, m, l, o, 3);
-        attend_chunk<1, true, VM>(Kl, Vt, qf, 192, p.Ntok, sl2, lane, false, m, l, o, 6);
+        attend_chunk<3, false>(Kl, Vt, qf, 0, p.Ntok, sl2, lane, true, m, l, o, 0);
+        attend_chunk<3, false>(Kl, Vt, qf, 96, p.Ntok, sl2, lane, false, m, l, o, 3);
+        attend_chunk<1, true>(Kl, Vt, qf, 192, p.Ntok, sl2, lane, false, m, l, o, 6);
     } else {
-        attend_chunk<3, false, VM>(Kl, Vt, qf, 0, p.Ntok, sl2, lane, true, m, l, o, 0);
-        if (p.Ntok > 96) attend_chunk<3, false, VM>(Kl, Vt, qf, 96, p.Ntok, sl2, lane, false, m, l, o, 3);
-        if (p.Ntok > 192) attend_chunk<1, false, VM>(Kl, Vt, qf, 192, p.Ntok, sl2, lane, false, m, l, o, 6);
+        attend_chunk<3, false>(Kl, Vt, qf, 0, p.Ntok, sl2, lane, true, m, l, o, 0);
+        if (p.Ntok > 96) attend_chunk<3, false>(Kl, Vt, qf, 96, p.Ntok, sl2, lane, false, m, l, o, 3);
+        if (p.Ntok > 192) attend_chunk<1, false>(Kl, Vt, qf, 192, p.Ntok, sl2, lane, false, m, l, o, 6);
     }
-    ATT_TRACE(5);
     if (q < p.Ntok) store_o(p, rowbase, q, h, bh, hf, m, l, o);
-    ATT_TRACE(6);
-}
-
-// Round 6: THREE (crop, head) units per CU -- built on VERDICT r5's lead, bit-identical, and a TIE with attn_fwd8_kernel (424-426 vs 419-422 us per
-// 1024-crop launch): the forward is no longer bound by units in flight, its VALU is busy 65-73 % of a launch (profiles/r06_c_attention_pipes.md).
-// NOT the default; CS_ATTN_FWD4=1 selects it (read per launch).  What it is:  attn_fwd8_kernel is bound by units in flight per CU x latency, not by a pipe: two units of 69 KB
-// alternate a 5.8 us load phase with a 4.5 us attend phase and for 29 % of a launch no unit of a CU is attending
-// (profiles/r04_t_attention_timeline.md).  A third resident unit needs <= 54.6 KB of LDS and, with eight waves per unit, <= 80 VGPRs -- the
-// attend phase holds 32 output + 16 query + 48 score registers.  So the unit shrinks instead: FOUR waves, each attending its query tiles one
-// after the other (tiles w and w + 4 of the seven; same attend_chunk, same 3 + 3 + 1 key chunks, hence the same bits), 12 waves per CU = three per
-// SIMD at <= 168 VGPRs, and LDS images sized for the sequence: K [200][64] (25.0 KB), V^T [64][200] (25.0 KB, layout 3 of attend_chunk) and
-// the RoPE tables stored ONCE: rope.py:118-142 builds the row part and the column part from the same `freqs` tensor and repeats every
-// frequency for the two dims of a pair, so cos_row[r][2j] == cos_row[r][2j+1] == cos_col[r][2j]: one [g][16] table each for cos and sin
-// (1.75 KB at g = 14 instead of 7 KB) -- a documented precondition of the C ABI (include/clipself_hip.h), checked by HipOps once per table.
-// 51.75 KB per unit.  For square grids up to 14 x 14 (Ntok <= 197).
-constexpr int K4_ROWS = 200;
-
-template <int NW, bool TAIL>
-__global__ __launch_bounds__(NW * 64, 3) void attn_fwd4_kernel(AttnArgs p) {     // 3 units per CU: 12 waves = 3 per SIMD (five waves per unit at 128 VGPRs spilled 31-46 dwords: 699 us)
-    constexpr int NT = NW * 64, KI = (K4_ROWS * 8 + NT - 1) / NT;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Kl = smem;
-    __bf16* Vt = (__bf16*)(smem + K4_ROWS * 128);
-    float* rt = (float*)(smem + K4_ROWS * 128 + HD * VT4_LD * 2);      // cos [g][16] | sin [g][16]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5, l31 = lane & 31;
-    const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-    const int C = p.H * HD;
-    const size_t rowbase = (size_t)b * p.Ntok;
-    const float sl2 = p.scale * LOG2E;
-    const int last = p.Ntok - 1;
-    // every global load of the workgroup ahead of the first dependent instruction: tables (oldest: vmcnt retires in order), K, V, Q of both tiles
-    float tab[2];
-    {
-        const int i = min(tid, p.grid * 16 - 1), r = i >> 4, j = i & 15;       // the column part of grid row 0: token r, dims 32 + 2j
-        tab[0] = p.cos_t[(size_t)r * HD + 32 + 2 * j];
-        tab[1] = p.sin_t[(size_t)r * HD + 32 + 2 * j];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    U128 kr[KI], vin[8], qraw[2][4];
-    const __bf16* kbase = p.qkv + C + h * HD;
-    const __bf16* vbase = p.qkv + 2 * C + h * HD;
-    const int vkb = min(tid, K4_ROWS - 1) >> 3, vc = tid & 7;      // one (key block, dim chunk) item per thread, threads >= 200 repeat the last
-#pragma unroll
-    for (int it = 0; it < KI; ++it) {          // branch-free: rows past the sequence re-read its last row (masked to p = 0 exactly)
-        const int idx = min(tid + it * NT, K4_ROWS * 8 - 1), tok = min(idx >> 3, last);
-        kr[it].u = *(const uint4*)(kbase + (rowbase + tok) * p.ldqkv + (idx & 7) * 8);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int tok = min(vkb * 8 + i, last);
-        vin[i].u = *(const uint4*)(vbase + (rowbase + tok) * p.ldqkv + vc * 8);
-    }
-    // the wave that owns a single query tile (seven tiles on NW waves) rotates with the unit index
-    int wq = wave + bh % NW;
-    wq = wq >= NW ? wq - NW : wq;
-#pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-        const int qc = min((wq + ps * NW) * 32 + l31, last);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qraw[ps][ks].u = *(const uint4*)(p.qkv + (rowbase + qc) * p.ldqkv + h * HD + ks * 16 + hf * 8);
-    }
-    if (tid < p.grid * 16) {
-        rt[tid] = tab[0];
-        rt[(p.grid << 4) + tid] = tab[1];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < KI; ++it) {          // K: rotate + swizzled LDS image
-        const int idx = tid + it * NT, r = idx >> 3, c = idx & 7;
-        if (idx < K4_ROWS * 8) {
-            if (r > 0 && r < p.Ntok) rope8c(kr[it], rt, p.grid, p.inv_grid, r, c);
-            *(uint4*)(Kl + k_off(r, c)) = kr[it].u;
-        }
-    }
-    if (tid < K4_ROWS) {                       // V: 8x8 in-register transpose -> V^T image, key block rotated by the dim chunk's upper bit
-        const int rot = vkb + (vc >> 2), pos = (rot >= 25 ? rot - 25 : rot) * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            U128 o;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o.e[i] = vin[i].e[j];
-            *(uint4*)(Vt + (vc * 8 + j) * VT4_LD + pos) = o.u;
-        }
-    }
-    __syncthreads();
-#pragma nounroll                               // one copy of the attend code: the second tile's rows are selected into the first's registers
-    for (int ps = 0; ps < 2; ++ps) {
-        const int q0 = (wq + ps * NW) * 32;
-        if (q0 >= p.Ntok) break;               // wave-uniform
-        // an opaque copy of the lane id: without it every lane mask and LDS address of the attend code is loop-invariant, gets hoisted in
-        // front of the loop and is spilled there (344 SGPRs in the first build)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int hf = ln >> 5, l31 = ln & 31;
-        const int q = q0 + l31, qc = min(q, last);
-        bf16x8 qf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            U128 t;
-            t.u = ps ? qraw[1][ks].u : qraw[0][ks].u;
-            if (qc > 0) rope8c(t, rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
-            qf[ks] = t.h;
-        }
-        float m = -INFINITY, l = 0.f;
-        f32x16 o[2] = {zero16(), zero16()};
-        if (TAIL) {                            // 192 < Ntok <= 200 (the 14x14 + CLS grid): two full chunks and the ragged last tile
-            attend_chunk<3, false, 3>(Kl, Vt, qf, 0, p.Ntok, sl2, ln, true, m, l, o, 0);
-            attend_chunk<3, false, 3>(Kl, Vt, qf, 96, p.Ntok, sl2, ln, false, m, l, o, 3);
-            attend_chunk<1, true, 3>(Kl, Vt, qf, 192, p.Ntok, sl2, ln, false, m, l, o, 6);
-        } else {
-            attend_chunk<3, false, 3>(Kl, Vt, qf, 0, p.Ntok, sl2, ln, true, m, l, o, 0);
-            if (p.Ntok > 96) attend_chunk<3, false, 3>(Kl, Vt, qf, 96, p.Ntok, sl2, ln, false, m, l, o, 3);
-            if (p.Ntok > 192) attend_chunk<1, false, 3>(Kl, Vt, qf, 192, p.Ntok, sl2, ln, false, m, l, o, 6);
-        }
-        if (q < p.Ntok) store_o(p, rowbase, q, h, bh, hf, m, l, o);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -1063,10 +789,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnArgs p) {
 // PRE (round 6): q and k come ROTATED from p.qk ([B*N, ldqk] bf16 = q | k, written once per launch by rope_qk_kernel): a workgroup of these
 // kernels walks the whole sequence, so the K rows (dQ kernel) and the Q rows (dK/dV kernel) of an (image, head) pair were rotated again by
 // every one of its 17 row blocks at the recipe's 4097 tokens -- a fifth of the kernels' VALU instructions.  Same rotation arithmetic, same bits.
+// Launched as <CH, true, false> (one chunk, rotated from the LDS tables) and <CH, false, true> (several chunks, prepass).  (Tried and removed:
+// several chunks without the prepass -- 5.5 % slower, 531 vs 502 us at 2 x 12 x 4097.  profiles/r06_f_long_sequence_prepass_ab.txt)
 template <int CH, bool SINGLE, bool PRE = false>
 __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnArgs p) {
     constexpr int CHK = CH * 32, NT = 512, NW = 8;
-    constexpr bool CT = false, PF = true;
+    constexpr bool PF = true;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kl = smem;
     char* Vl = smem + CHK * 128;
@@ -1094,7 +822,7 @@ __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnA
     } else {
         load_rope_tables<NT>(rt, p.cos_t, p.sin_t, p.grid, tid);
         __syncthreads();
-        load_q_frags<CT>(p, rt, rowbase, qc, h, hf, qf);
+        load_q_frags(p, rt, rowbase, qc, h, hf, qf);
     }
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) dof[ks] = *(const bf16x8*)(p.dout + (rowbase + qc) * p.ldo + h * HD + ks * 16 + hf * 8);
@@ -1115,7 +843,7 @@ __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnA
 
     for (int key0 = 0; key0 < (SINGLE ? 1 : p.Ntok); key0 += CHK) {
         if (key0) __syncthreads();                     // every wave is done with the previous chunk's images
-        kr.template store<!PRE, true, CT>(Kl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
+        kr.template store<!PRE, true>(Kl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
         vr.template store<false>(Vl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
         __syncthreads();
         if (!SINGLE && PF && key0 + CHK < p.Ntok) {    // the next chunk's rows travel while this one is consumed
@@ -1177,7 +905,7 @@ __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnA
 template <int CH, bool SINGLE, bool PRE = false>
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {       // 64 + 32 + 32 accumulator / operand registers: no 128-register form
     constexpr int CHQ = CH * 32, NT = 512, NW = 8;
-    constexpr bool CT = false, PF = true;
+    constexpr bool PF = true;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ql = smem;
     char* Gl = smem + CHQ * 128;
@@ -1241,7 +969,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {    
 
     for (int q0 = 0; q0 < (SINGLE ? 1 : p.Ntok); q0 += CHQ) {
         if (q0) __syncthreads();
-        qr.template store<!PRE, false, CT>(Ql, rt, p.grid, p.inv_grid, q0, p.Ntok, tid);
+        qr.template store<!PRE>(Ql, rt, p.grid, p.inv_grid, q0, p.Ntok, tid);
         gr.template store<false>(Gl, rt, p.grid, p.inv_grid, q0, p.Ntok, tid);
         if (tid < CHQ) { lse_s[tid] = lse_r; dsum_s[tid] = dsum_r; }
         __syncthreads();
@@ -1339,7 +1067,7 @@ int check_common(const char* who, int B, int Ntok, int H, int ldqkv, int ldo) {
 //   * one workgroup per (crop, group of HG heads); a key's 64 head-dim values are spread over 8 lanes (16 B each), so a wave
 //     reads 8 whole 128-byte key rows per instruction and the RoPE table entries of a (key, chunk) are loaded once and
 //     reused across the HG heads;
-//   * arithmetic mirrors attn_fwd_kernel: keys 1.. rotated and rounded to bf16, fp32 scores, exp2(s - max) rounded to
+//   * arithmetic mirrors the forward kernels: keys 1.. rotated and rounded to bf16, fp32 scores, exp2(s - max) rounded to
 //     bf16 for the P.V product, fp32 row sum of the unrounded exponentials.
 // Round 4: the same kernel serves the OpenAI-CLIP family's extra query tokens (cs_attn_query_fwd: open_clip/transformer.py:736-834) -- qpb
 // query rows share one image's keys / values, `allow` [queries][Ntok] says which keys a query may attend (no rotary tables there).
@@ -1457,82 +1185,29 @@ static int attn_fwd_impl(const void* qkv, const float* cos_t, const float* sin_t
 #ifdef CS_ABLATION_SWITCHES
     static const int dbg_env = getenv("CS_ATTN_DBG") ? atoi(getenv("CS_ATTN_DBG")) : 0;
     a.dbg = dbg_env;
-    static const char* trace_path = getenv("CS_ATTN_TRACE");
-    static unsigned long long* trace_buf = nullptr;
-    static size_t trace_cap = 0;
-    if (trace_path && trace_cap < (size_t)B * H * 64) {
-        if (trace_buf) (void)hipFree(trace_buf);
-        trace_cap = (size_t)B * H * 64;
-        if (hipMalloc((void**)&trace_buf, trace_cap) != hipSuccess) { trace_buf = nullptr; trace_cap = 0; }
-    }
-    a.trace = trace_buf;
 #else
     a.dbg = 0;
 #endif
     a.Ntok = Ntok; a.H = H; a.ldqkv = ldqkv; a.ldo = ldo; a.scale = scale;
     constexpr int CH = 7;
-    static const size_t lds_pad = getenv("CS_ATTN_LDSPAD") ? (size_t)atoi(getenv("CS_ATTN_LDSPAD")) : 0;     // occupancy experiments
-    const size_t lds = (size_t)CH * 32 * 128 + (size_t)HD * VT_LD * 2 + (size_t)4 * g * 32 * sizeof(float) + lds_pad;
+    const size_t lds = (size_t)CH * 32 * 128 + (size_t)HD * VT_LD * 2 + (size_t)4 * g * 32 * sizeof(float);
     CS_CHECK_ARG(lds <= 160 * 1024, "cs_attn_fwd: token grid %d too large for the LDS RoPE tables", g);
-    // A/B switch, read per launch: CS_ATTN_FWD4=1 = four waves per unit, three units per CU (round 6: a tie, see attn_fwd4_kernel)
-    const char* f4 = getenv("CS_ATTN_FWD4");
-    if (f4 && f4[0] == '1' && Ntok <= K4_ROWS && g <= 14) {
-        static bool once4 = (set_lds(attn_fwd4_kernel<4, false>, 160 * 1024), set_lds(attn_fwd4_kernel<4, true>, 160 * 1024), true);
-        (void)once4;
-        const size_t lds4 = (size_t)K4_ROWS * 128 + (size_t)HD * VT4_LD * 2 + (size_t)2 * g * 16 * sizeof(float) + lds_pad;
-        if (getenv("CS_ATTN_DEBUG")) {
-            int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, attn_fwd4_kernel<4, true>, 256, lds4);
-            fprintf(stderr, "[cs_attn] fwd4: %d resident workgroups per CU (lds %zu)\n", nb, lds4);
-        }
-        if (Ntok > 192) hipLaunchKernelGGL((attn_fwd4_kernel<4, true>), dim3(1, B * H), dim3(256), lds4, stream, a);
-        else hipLaunchKernelGGL((attn_fwd4_kernel<4, false>), dim3(1, B * H), dim3(256), lds4, stream, a);
-    } else if (Ntok <= CH * 32) {
+    if (Ntok <= CH * 32) {
         // whole sequence in one LDS image: eight waves, one query tile each, two workgroups (16 waves) per CU; when only the last key tile is
         // ragged (Ntok > 32 (CH - 1): the 14x14 grid), the variant whose ragged-tile code exists once
-        static bool once = (set_lds(attn_fwd8_kernel<false, 0>, 160 * 1024), set_lds(attn_fwd8_kernel<true, 0>, 160 * 1024),
-                            set_lds(attn_fwd8_kernel<false, 1>, 160 * 1024), set_lds(attn_fwd8_kernel<true, 1>, 160 * 1024), true);
+        static bool once = (set_lds(attn_fwd8_kernel<false>, 160 * 1024), set_lds(attn_fwd8_kernel<true>, 160 * 1024), true);
         (void)once;
-        // A/B switch, read per launch.  Default: the transposed V image of rounds 1-4.  CS_ATTN_FWD8_VROW=1: V row-major + transposing reads --
-        // bit-identical outputs, measured 2 % SLOWER per 2048-crop launch (811-816 -> 830-831 us, profiles/r05_h_fwd8_row_major_v.txt): the
-        // 8-byte transposing reads double the V fragment instructions of the attend phase and meet 2-way bank conflicts, which costs more than
-        // the in-register transposes of the staging phase save.
-        const bool vt = getenv("CS_ATTN_FWD8_VROW") == nullptr;
-        const size_t lds8 = vt ? lds : (size_t)2 * CH * 32 * 128 + (size_t)4 * g * 32 * sizeof(float) + lds_pad;
-        if (getenv("CS_ATTN_DEBUG")) {
-            int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, attn_fwd8_kernel<true, 0>, 512, lds8);
-            fprintf(stderr, "[cs_attn] fwd8: %d resident workgroups per CU (lds %zu)\n", nb, lds8);
-        }
-        const bool tail = Ntok > (CH - 1) * 32;
-        if (vt) {
-            if (tail) hipLaunchKernelGGL((attn_fwd8_kernel<true, 0>), dim3(1, B * H), dim3(512), lds8, stream, a);
-            else hipLaunchKernelGGL((attn_fwd8_kernel<false, 0>), dim3(1, B * H), dim3(512), lds8, stream, a);
-        } else {
-            if (tail) hipLaunchKernelGGL((attn_fwd8_kernel<true, 1>), dim3(1, B * H), dim3(512), lds8, stream, a);
-            else hipLaunchKernelGGL((attn_fwd8_kernel<false, 1>), dim3(1, B * H), dim3(512), lds8, stream, a);
-        }
+        if (Ntok > (CH - 1) * 32) hipLaunchKernelGGL((attn_fwd8_kernel<true>), dim3(1, B * H), dim3(512), lds, stream, a);
+        else hipLaunchKernelGGL((attn_fwd8_kernel<false>), dim3(1, B * H), dim3(512), lds, stream, a);
     } else {
-        static bool once = (set_lds(attn_fwd_kernel<CH>, 160 * 1024), set_lds(attn_fwd2_kernel<CH, 4>, 160 * 1024), true);
+        static bool once = (set_lds(attn_fwd2_kernel<CH, 4>, 160 * 1024), true);
         (void)once;
-        if (getenv("CS_ATTN_FWD_V1")) {                    // A/B switch, read per launch: the synchronous round-1 form
-            hipLaunchKernelGGL((attn_fwd_kernel<CH>), dim3((Ntok + 255) / 256, B * H), dim3(512), lds, stream, a);
-        } else {
-            const size_t lds2 = (size_t)2 * CH * 32 * 128 + (size_t)4 * g * 32 * sizeof(float);
-            dim3 grid2;
-            set_schedule(a, B, Ntok, H, grid2);
-            hipLaunchKernelGGL((attn_fwd2_kernel<CH, 4>), grid2, dim3(512), lds2, stream, a);
-        }
+        const size_t lds2 = (size_t)2 * CH * 32 * 128 + (size_t)4 * g * 32 * sizeof(float);
+        dim3 grid2;
+        set_schedule(a, B, Ntok, H, grid2);
+        hipLaunchKernelGGL((attn_fwd2_kernel<CH, 4>), grid2, dim3(512), lds2, stream, a);
     }
     CS_LAUNCH_CHECK();
-#ifdef CS_ABLATION_SWITCHES
-    if (a.trace && Ntok <= CH * 32) {     // the LAST launch's timeline survives in the file
-        (void)hipStreamSynchronize(stream);
-        std::vector<unsigned long long> host((size_t)B * H * 8);
-        (void)hipMemcpy(host.data(), a.trace, host.size() * 8, hipMemcpyDeviceToHost);
-        if (FILE* f = fopen(trace_path, "wb")) { fwrite(host.data(), 8, host.size(), f); fclose(f); }
-    }
-#endif
     return 0;
 }
 
@@ -1579,8 +1254,7 @@ extern "C" int cs_attn_bwd(const void* qkv, const void* o, const void* dout, con
         const size_t rope = (size_t)4 * g * 32 * sizeof(float);
         const size_t lds_dq = (size_t)2 * CHK * 128 + rope, lds_dkv = (size_t)2 * CHK * 128 + (size_t)2 * CHK * sizeof(float) + rope;
         CS_CHECK_ARG(lds_dkv <= 160 * 1024, "cs_attn_bwd: token grid %d too large for the LDS RoPE tables", g);
-        static bool once = (set_lds(attn_bwd_dq2_kernel<CH, false>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, false>, 160 * 1024),
-                            set_lds(attn_bwd_dq2_kernel<CH, true>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, true>, 160 * 1024),
+        static bool once = (set_lds(attn_bwd_dq2_kernel<CH, true>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, true>, 160 * 1024),
                             set_lds(attn_bwd_dq2_kernel<CH, false, true>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, false, true>, 160 * 1024), true);
         (void)once;
         if (Ntok <= CHK) {
@@ -1590,22 +1264,16 @@ extern "C" int cs_attn_bwd(const void* qkv, const void* o, const void* dout, con
         } else {
             dim3 grid2;
             set_schedule(a, B, Ntok, H, grid2);
-            if (getenv("CS_ATTN_NOPRE")) {                 // A/B switch, read per launch: every row block rotates its operands itself (round 5)
-                hipLaunchKernelGGL((attn_bwd_dq2_kernel<CH, false>), grid2, block, lds_dq, stream, a);
-                CS_LAUNCH_CHECK();
-                hipLaunchKernelGGL((attn_bwd_dkv2_kernel<CH, false>), grid2, block, lds_dkv, stream, a);
-            } else {
-                const int C2 = 2 * H * HD;
-                __bf16* qk = (__bf16*)((char*)workspace + bwd_dsum_bytes(B, Ntok, H));
-                const long items = (long)B * Ntok * (C2 / 8);
-                hipLaunchKernelGGL(rope_qk_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, (const __bf16*)qkv, cos_t, sin_t, qk,
-                                   (long)B * Ntok, Ntok, H * HD, ldqkv);
-                CS_LAUNCH_CHECK();
-                a.qk = qk; a.ldqk = C2;
-                hipLaunchKernelGGL((attn_bwd_dq2_kernel<CH, false, true>), grid2, block, lds_dq - rope, stream, a);
-                CS_LAUNCH_CHECK();
-                hipLaunchKernelGGL((attn_bwd_dkv2_kernel<CH, false, true>), grid2, block, lds_dkv - rope, stream, a);
-            }
+            const int C2 = 2 * H * HD;
+            __bf16* qk = (__bf16*)((char*)workspace + bwd_dsum_bytes(B, Ntok, H));
+            const long items = (long)B * Ntok * (C2 / 8);
+            hipLaunchKernelGGL(rope_qk_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, (const __bf16*)qkv, cos_t, sin_t, qk,
+                               (long)B * Ntok, Ntok, H * HD, ldqkv);
+            CS_LAUNCH_CHECK();
+            a.qk = qk; a.ldqk = C2;
+            hipLaunchKernelGGL((attn_bwd_dq2_kernel<CH, false, true>), grid2, block, lds_dq - rope, stream, a);
+            CS_LAUNCH_CHECK();
+            hipLaunchKernelGGL((attn_bwd_dkv2_kernel<CH, false, true>), grid2, block, lds_dkv - rope, stream, a);
         }
         CS_LAUNCH_CHECK();
         return 0;

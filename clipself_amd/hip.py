@@ -333,11 +333,11 @@ class HipOps:
         self._ok(self.lib.cs_ln_stats_finalize(_p(part), P, npp, C, M, eps, _p(mean), _p(rstd), self._stream()), "cs_ln_stats_finalize")
 
     def _check_rope_tables(self, cos, sin, Ntok):
-        """The forward kernels read the rotary tables separably and (round 6, attn_fwd4_kernel) ONCE per frequency: for a g x g grid, dims
-        [0, 32) of token (r, c) depend on r only, dims [32, 64) on c only, the row part of grid row i equals the column part of grid column i,
-        and the two dims of a rotation pair share their entry -- exactly what rope.py:118-142 builds (one `freqs` tensor, repeated for the
-        pair, broadcast over rows and columns).  The C ABI documents this as a precondition (include/clipself_hip.h); this wrapper checks it
-        once per table tensor (a few reductions and one host read-back) and raises instead of letting a kernel return wrong numbers."""
+        """The rotary tables must have the layout rope.py:118-142 builds (one `freqs` tensor, repeated for the pair, broadcast over rows and
+        columns): for a g x g grid, dims [0, 32) of token (r, c) depend on r only, dims [32, 64) on c only (the forward kernels read the tables
+        separably), the row part of grid row i equals the column part of grid column i, and the two dims of a rotation pair share their entry.
+        The C ABI documents this as a precondition (include/clipself_hip.h); this wrapper checks it once per table tensor (a few reductions
+        and one host read-back) and raises instead of letting a kernel return wrong numbers."""
         def ver(t):
             try:
                 return t._version

@@ -128,8 +128,8 @@ def test_tower_partition_arguments_are_validated_at_construction(monkeypatch):
 
 
 def test_rotary_table_layout_is_checked_by_the_wrapper():
-    """Round 6: the attention kernels read the rotary tables separably and (attn_fwd4_kernel) once per frequency -- the layout rope.py:118-142 builds
-    is a documented precondition of the C ABI.  HipOps verifies it once per table tensor: the oracle's tables and identity tables (the OpenAI-CLIP
+    """Round 6: the layout rope.py:118-142 builds (separable, row part == column part, one entry per rotation pair) is a documented
+    precondition of the C ABI.  HipOps verifies it once per table tensor: the oracle's tables and identity tables (the OpenAI-CLIP
     family) pass, also as inference tensors; a table whose row part differs from its column part, whose pair entries differ, or that is not
     separable raises instead of letting a kernel return wrong numbers.  (No GPU: the object is built around the logic.)"""
     import torch

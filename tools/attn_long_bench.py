@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """cs_attn_fwd (with lse) and cs_attn_bwd on a g x g (+CLS) token grid: microseconds per launch and the share of the MFMA peak (forward 4 N^2 d,
-backward 10 N^2 d FLOPs per head), for the round-1 kernels (CS_ATTN_FWD_V1 / CS_ATTN_BWD_V1, read per launch) and the current ones, interleaved.
+backward 10 N^2 d FLOPs per head), interleaved: the round-1 backward (CS_ATTN_BWD_V1, read per launch; the forward is the current kernel in
+both passes) and the current kernels.
 usage (GPU box): python tools/attn_long_bench.py [images [grid [heads [reps]]]]     e.g. 2 64 12 (the recipe's 4097 tokens), 64 14 12, 16 24 16"""
 import os
 import sys
@@ -47,11 +48,10 @@ def timed(fn):
 ffl, bfl = 4.0 * N * N * 64 * B * H, 10.0 * N * N * 64 * B * H
 for rnd in range(2):
     for ver in ("v1", "v2"):
-        for k in ("CS_ATTN_FWD_V1", "CS_ATTN_BWD_V1"):
-            if ver == "v1":
-                os.environ[k] = "1"
-            else:
-                os.environ.pop(k, None)
+        if ver == "v1":
+            os.environ["CS_ATTN_BWD_V1"] = "1"
+        else:
+            os.environ.pop("CS_ATTN_BWD_V1", None)
         f = timed(lambda: ops.attn_fwd(qkv, cos, sin, out, lse, B, N, H, 0.125))
         b = timed(lambda: ops.attn_bwd(qkv, out, dout, lse, cos, sin, dqkv, ws, B, N, H, 0.125))
         print(f"{B} images x {H} heads x {N} tokens, {ver} pass {rnd}: fwd {f:8.1f} us = {ffl / f / 1e6 / PEAK:.3f} of peak | "
