@@ -42,7 +42,10 @@ __device__ __forceinline__ void store_x4(float* p, const float (&v)[4]) { *(floa
 // Q8 (bf16 output only): the row also leaves as e4m3 bytes with one fp32 scale -- the A operand of the fp8 GEMM that consumes this
 // LayerNorm (cs_gemm_nt_f8), quantised from the ROUNDED bf16 values exactly as cs_quant_rows_fp8 would from y (same amax / 448 scale,
 // same v_cvt_pk_fp8_f32), columns C .. Kp-1 zero: the quantiser's pass over y (read 2 B, write 1 B per element, one launch) disappears.
-template <typename TX, int MAXG, typename TY = __bf16, bool Q8 = false>
+// RAG (C % 4 != 0, rows padded to the next multiple of 4): the row ends inside its last vector.  Every reduction and gamma / beta are then
+// masked per element, so that whatever the 1-3 pad columns of x / gamma / beta hold (NaN included) reaches no result, and the pad columns
+// of y are written as exact zeros.  The C % 4 == 0 instantiations carry none of this.
+template <typename TX, int MAXG, typename TY = __bf16, bool Q8 = false, bool RAG = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, long ldx, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, TY* __restrict__ y, long ldy,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, l
         const int c = (g * 64 + lane) * 4;
         Vec4<TX>::cvt(xr_raw[g], v[g]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[g][i] = (g < ng && c < C) ? v[g][i] : 0.f;
+        for (int i = 0; i < 4; ++i) v[g][i] = (g < ng && (RAG ? c + i < C : c < C)) ? v[g][i] : 0.f;
         s += (v[g][0] + v[g][1]) + (v[g][2] + v[g][3]);
     }
     const float mean = wave_sum(s) / (float)C;
@@ -98,6 +101,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const TX* __restrict__ x, l
             if (g < ng && c < C) {
                 float o[4] = {(v[g][0] - mean) * rstd * ga[g].x + be[g].x, (v[g][1] - mean) * rstd * ga[g].y + be[g].y,
                               (v[g][2] - mean) * rstd * ga[g].z + be[g].z, (v[g][3] - mean) * rstd * ga[g].w + be[g].w};
+                if (RAG) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o[i] = (c + i < C) ? o[i] : 0.f;      // a select: NaN in the pad of x / gamma / beta ends here
+                }
                 store_x4(yr + c, o);
                 if (Q8) {
 #pragma unroll
@@ -219,7 +226,8 @@ enum { DX_BF16 = 0, DX_F32_ASSIGN = 1, DX_F32_ACCUM = 2 };
 // its column sums -- the bias gradient of the linear layer in front of this LayerNorm's residual branch -- ride along as a third
 // partial row: the `cast_f32_bf16` + `colsum_bf16` passes over the stream that used to follow every such LayerNorm backward are gone,
 // and the sums are combined in a fixed order (no atomics).
-template <typename TX, int DXMODE, int MAXG, bool COPY>
+// RAG: as in ln_fwd_kernel -- per-element masks on dy, x and gamma, exact zeros into the pad columns of dx / dx_copy (accumulate mode too).
+template <typename TX, int DXMODE, int MAXG, bool COPY, bool RAG = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ dy, long lddy, const TX* __restrict__ x, long ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean_in,
                                                      const float* __restrict__ rstd_in, void* __restrict__ dx, long lddx,
@@ -242,7 +250,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
         const int c = (g * 64 + lane) * 4;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { dg[g][i] = 0.f; db[g][i] = 0.f; ga[g][i] = 0.f; if (COPY) dc[g][i] = 0.f; }
-        if (g < ng && c < C) { const float4 t = *(const float4*)(gamma + c); ga[g][0] = t.x; ga[g][1] = t.y; ga[g][2] = t.z; ga[g][3] = t.w; }
+        if (g < ng && c < C) {
+            const float4 t = *(const float4*)(gamma + c);
+            ga[g][0] = t.x; ga[g][1] = t.y; ga[g][2] = t.z; ga[g][3] = t.w;
+            if (RAG) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ga[g][i] = (c + i < C) ? ga[g][i] : 0.f;
+            }
+        }
     }
     for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
         const float mean = mean_in[row], rstd = rstd_in[row];
@@ -266,8 +281,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
             Vec4<__bf16>::cvt(d_raw[g], dv[g]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float d = ok ? dv[g][i] : 0.f;
-                xh[g][i] = ok ? (xv[g][i] - mean) * rstd : 0.f;
+                const bool oki = RAG ? (ok && c + i < C) : ok;
+                const float d = oki ? dv[g][i] : 0.f;
+                xh[g][i] = oki ? (xv[g][i] - mean) * rstd : 0.f;
                 gy[g][i] = d * ga[g][i];
                 s1 += gy[g][i];
                 s2 += gy[g][i] * xh[g][i];
@@ -292,7 +308,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
                     float* p = (float*)dx + (size_t)row * lddx + c;
                     if (DXMODE == DX_F32_ACCUM) {
                         const float4 t = *(const float4*)p;
-                        o[0] += t.x; o[1] += t.y; o[2] += t.z; o[3] += t.w;
+                        const float tv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) o[i] += (!RAG || c + i < C) ? tv[i] : 0.f;     // RAG: the pad columns leave as zeros
                     }
                     *(float4*)p = make_float4(o[0], o[1], o[2], o[3]);
                     if (COPY) {
@@ -448,26 +466,30 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 // x_dtype: 0 = f32, 1 = bf16.  mean/rstd may be null (teacher, no backward).
 static int layernorm_fwd_impl(const void* x, int x_dtype, long ldx, const float* gamma, const float* beta, void* y, long ldy, float* mean,
                               float* rstd, int M, int C, float eps, void* q8, long ldq, float* q_scale, hipStream_t stream) {
-    // C % 4 != 0 is allowed for zero-padded rows: x, y, gamma, beta must then be readable/writable up to the next multiple of 4
-    // (padding zero in x/gamma/beta -> the padding of y comes out zero).
-    CS_CHECK_ARG(C <= MAXC && (C % 4 == 0 || (ldx >= ((C + 3) & ~3) && ldy >= ((C + 3) & ~3))), "cs_layernorm_fwd: C=%d unsupported (ld too small for a padded row, or > %d)", C, MAXC);
+    // C % 4 != 0 is allowed for padded rows: x, y, gamma, beta must then be readable / writable up to the next multiple of 4.  What the
+    // pad columns of x / gamma / beta hold is ignored, the pad columns of y are written as zeros (the RAG instantiations).
+    CS_CHECK_ARG(C <= MAXC && (C % 4 == 0 || (ldx >= ((C + 3) & ~3) && (y == nullptr || ldy >= ((C + 3) & ~3)))), "cs_layernorm_fwd: C=%d unsupported (ld too small for a padded row, or > %d)", C, MAXC);
     CS_CHECK_ARG(M > 0, "cs_layernorm_fwd: empty input");
     dim3 grid((M + ROWS_PER_WG - 1) / ROWS_PER_WG), block(256);
     if (q8 != nullptr) {
         const int Kp = (C + 127) / 128 * 128;
         CS_CHECK_ARG(y != nullptr && q_scale != nullptr && ldq >= Kp && ldq % 4 == 0 && ((uintptr_t)q8 % 4) == 0 && Kp <= 256 * 12,
                      "cs_layernorm_fwd_q8: needs y, the scale vector and 4-byte aligned e4m3 rows of >= %d bytes", Kp);
-#define LNQ(TX, NG) hipLaunchKernelGGL((ln_fwd_kernel<TX, NG, __bf16, true>), grid, block, 0, stream, (const TX*)x, ldx, gamma, beta, (__bf16*)y, ldy, mean, rstd, M, C, eps, (unsigned char*)q8, ldq, q_scale, Kp)
+#define LNQ2(TX, NG, RG) hipLaunchKernelGGL((ln_fwd_kernel<TX, NG, __bf16, true, RG>), grid, block, 0, stream, (const TX*)x, ldx, gamma, beta, (__bf16*)y, ldy, mean, rstd, M, C, eps, (unsigned char*)q8, ldq, q_scale, Kp)
+#define LNQ(TX, NG) do { if (C % 4 == 0) LNQ2(TX, NG, false); else LNQ2(TX, NG, true); } while (0)
         if (x_dtype == 0) { if (Kp <= 1024) LNQ(float, 4); else if (Kp <= 2048) LNQ(float, 8); else LNQ(float, 12); }
         else { if (Kp <= 1024) LNQ(__bf16, 4); else if (Kp <= 2048) LNQ(__bf16, 8); else LNQ(__bf16, 12); }
 #undef LNQ
+#undef LNQ2
         CS_LAUNCH_CHECK();
         return 0;
     }
-#define LNF(TX, NG) hipLaunchKernelGGL((ln_fwd_kernel<TX, NG>), grid, block, 0, stream, (const TX*)x, ldx, gamma, beta, (__bf16*)y, ldy, mean, rstd, M, C, eps)
+#define LNF2(TX, NG, RG) hipLaunchKernelGGL((ln_fwd_kernel<TX, NG, __bf16, false, RG>), grid, block, 0, stream, (const TX*)x, ldx, gamma, beta, (__bf16*)y, ldy, mean, rstd, M, C, eps)
+#define LNF(TX, NG) do { if (C % 4 == 0) LNF2(TX, NG, false); else LNF2(TX, NG, true); } while (0)
     if (x_dtype == 0) { if (C <= 1024) LNF(float, 4); else if (C <= 2048) LNF(float, 8); else LNF(float, 12); }
     else { if (C <= 1024) LNF(__bf16, 4); else if (C <= 2048) LNF(__bf16, 8); else LNF(__bf16, 12); }
 #undef LNF
+#undef LNF2
     CS_LAUNCH_CHECK();
     return 0;
 }
@@ -540,13 +562,14 @@ static int layernorm_bwd_impl(const void* dy, long lddy, const void* x, int x_dt
     const int NR = copy ? 3 : 2;
     const size_t lds = (size_t)3 * NR * ((C + 3) & ~3) * sizeof(float);
     dim3 grid(nwg), block(256);
-#define LNB4(TX, MODE, NG, CP)                                                                                              \
+#define LNB5(TX, MODE, NG, CP, RG)                                                                                          \
     do {                                                                                                                    \
-        static bool once = (hipFuncSetAttribute((const void*)ln_bwd_kernel<TX, MODE, NG, CP>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 3 * MAXC * 4), true); \
+        static bool once = (hipFuncSetAttribute((const void*)ln_bwd_kernel<TX, MODE, NG, CP, RG>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 3 * MAXC * 4), true); \
         (void)once;                                                                                                         \
-        hipLaunchKernelGGL((ln_bwd_kernel<TX, MODE, NG, CP>), grid, block, lds, stream, (const __bf16*)dy, lddy, (const TX*)x, ldx, gamma, mean, rstd, dx, lddx, \
+        hipLaunchKernelGGL((ln_bwd_kernel<TX, MODE, NG, CP, RG>), grid, block, lds, stream, (const __bf16*)dy, lddy, (const TX*)x, ldx, gamma, mean, rstd, dx, lddx, \
                            (__bf16*)dx_copy, ldcopy, part, M, C, (unsigned char*)q8, ldq, q_scale, Kp);                     \
     } while (0)
+#define LNB4(TX, MODE, NG, CP) do { if (C % 4 == 0) LNB5(TX, MODE, NG, CP, false); else LNB5(TX, MODE, NG, CP, true); } while (0)
 #define LNB3(TX, MODE, NG) do { if (copy) { if constexpr (MODE != DX_BF16) LNB4(TX, MODE, NG, true); } else LNB4(TX, MODE, NG, false); } while (0)
 #define LNB(TX, MODE) do { if (C <= 1024) LNB3(TX, MODE, 4); else if (C <= 2048) LNB3(TX, MODE, 8); else LNB3(TX, MODE, 12); } while (0)
     if (x_dtype == 0) {
@@ -557,6 +580,7 @@ static int layernorm_bwd_impl(const void* dy, long lddy, const void* x, int x_dt
 #undef LNB
 #undef LNB3
 #undef LNB4
+#undef LNB5
     CS_LAUNCH_CHECK();
     if (need_part) {
         hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((NR * ((C + 3) & ~3) + 15) / 16), dim3(256), 0, stream, part, nwg, C, NR, dgamma, dbeta,

@@ -121,6 +121,11 @@ def _dt(t) -> int:
     raise TypeError(f"unsupported dtype {t.dtype}")
 
 
+def _readable(t, n) -> bool:
+    """True when n elements from t's first one lie inside its storage (a kernel may fetch that many in whole vectors)."""
+    return t is None or t.untyped_storage().nbytes() - t.storage_offset() * t.element_size() >= n * t.element_size()
+
+
 class HipOps:
     """Tensor-level face of the C ABI.  Tensors are 2-D (rows, cols) views whose last stride is 1; row strides
     become the `ld*` arguments.  Outputs are written in place into caller-allocated tensors."""
@@ -368,11 +373,19 @@ class HipOps:
         self._ok(self.lib.cs_attn_fwd_stats(_p(qkv), _p(cos), _p(sin), _p(out), _p(lse), _p(stats_part), B, Ntok, H, qkv.stride(0),
                                             out.stride(0), scale, self._stream()), "cs_attn_fwd_stats")
 
+    @staticmethod
+    def _ln_pad(C, *params):
+        """C % 4 != 0 (padded rows): the kernels fetch gamma / beta in 16-byte pieces, so these must be readable up to the next multiple of 4
+        (include/clipself_hip.h, cs_layernorm_fwd); what the extra elements hold is ignored."""
+        if C % 4:
+            assert all(_readable(t, (C + 3) // 4 * 4) for t in params), "LayerNorm with C % 4 != 0: gamma / beta must be readable up to roundup4(C)"
+
     def layernorm_fwd(self, x, gamma, beta, y, mean=None, rstd=None, eps=1e-6, q8=None, q_scale=None):
         if q8 is not None:
             return self.layernorm_fwd_q8(x, gamma, beta, y, q8, q_scale, mean, rstd, eps)
         self._chk(x, gamma, beta, y, mean, rstd)
         M, C = x.shape
+        self._ln_pad(C, gamma, beta)
         self._ok(self.lib.cs_layernorm_fwd(_p(x), _dt(x), x.stride(0), _p(gamma), _p(beta), _p(y), y.stride(0) if y is not None else 0,
                                            _p(mean), _p(rstd), M, C, eps, self._stream()), "cs_layernorm_fwd")
 
@@ -382,6 +395,7 @@ class HipOps:
         self._chk(x, gamma, beta, y, mean, rstd, q8, q_scale)
         M, C = x.shape
         assert q8.element_size() == 1 and q8.stride(1) == 1 and q8.shape[1] >= (C + 127) // 128 * 128 and q_scale is not None and y is not None
+        self._ln_pad(C, gamma, beta)
         self._ok(self.lib.cs_layernorm_fwd_q8(_p(x), _dt(x), x.stride(0), _p(gamma), _p(beta), _p(y), y.stride(0), _p(mean), _p(rstd),
                                               _p(q8), q8.stride(0), _p(q_scale), M, C, eps, self._stream()), "cs_layernorm_fwd_q8")
 
@@ -402,6 +416,7 @@ class HipOps:
         self._chk(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, dx_copy, copy_colsum, q8, q_scale)
         M, C = x.shape
         assert dx_copy is not None and dx_copy.dtype == torch.bfloat16 and dx_copy.shape == (M, C) and dx_copy.stride(1) == 1
+        self._ln_pad(C, gamma)
         assert q8.element_size() == 1 and q8.stride(1) == 1 and q8.shape[1] >= (C + 127) // 128 * 128 and q_scale is not None
         self._ok(self.lib.cs_layernorm_bwd_q8(_p(dy), dy.stride(0), _p(x), _dt(x), x.stride(0), _p(gamma), _p(mean), _p(rstd),
                                               _p(dx), dx_mode, dx.stride(0), _p(dgamma), _p(dbeta), int(accumulate),
@@ -417,6 +432,7 @@ class HipOps:
                                          q8, q_scale)
         self._chk(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, dx_copy, copy_colsum)
         M, C = x.shape
+        self._ln_pad(C, gamma)
         if dx_copy is not None:
             assert dx_copy.dtype == torch.bfloat16 and dx_copy.shape == (M, C) and dx_copy.stride(1) == 1
         self._ok(self.lib.cs_layernorm_bwd(_p(dy), dy.stride(0), _p(x), _dt(x), x.stride(0), _p(gamma), _p(mean), _p(rstd),
@@ -556,6 +572,7 @@ class HipOps:
         self._chk(img, out)
         B, _, S, _ = img.shape
         assert img.is_contiguous()
+        assert out.stride(1) == 1 and out.stride(0) == out.shape[1], "im2row writes whole rows (zeros in [3*p*p, ldo)): out must be contiguous"
         self._ok(self.lib.cs_im2row(_p(img), _dt(img), _p(out), B, S, p, out.stride(0), self._stream()), "cs_im2row")
 
     def cls_row(self, x, cls, pos):
@@ -595,6 +612,7 @@ class HipOps:
 
     def fed_bce_bwd(self, logits, tgt, dz, ns, temp, weight, upstream=None):
         self._chk(logits, tgt, dz, upstream)
+        assert dz.stride(1) == 1 and dz.stride(0) == dz.shape[1], "fed_bce_bwd writes whole rows (zeros in [ns, ldd)): dz must be contiguous"
         self._ok(self.lib.cs_fed_bce_bwd(_p(logits), logits.stride(0), _p(tgt), _p(dz), dz.stride(0), logits.shape[0], ns, temp, weight,
                                          _p(upstream), self._stream()), "cs_fed_bce_bwd")
 

@@ -93,7 +93,11 @@ int cs_gemm_nt_ln_split(const void* A, const void* B, const float* bias, const f
 
 /* --- LayerNorm(eps, biased var): src/open_clip/eva_clip/transformer.py:52-58 used at eva_vit_model.py:306-307 (norm1/2),
  *     :218 (inner_attn_ln), :102 (ffn_ln), :565/:616 (final norm); replaces apex FusedLayerNorm / F.layer_norm.
- * x_dtype 0=f32 1=bf16; y bf16 (NULL = statistics only); mean/rstd [M] f32 (nullable when no backward is needed). */
+ * x_dtype 0=f32 1=bf16; y bf16 (NULL = statistics only); mean/rstd [M] f32 (nullable when no backward is needed).
+ * C % 4 != 0 (padded rows, e.g. 2730 hidden units in 2752-wide storage) needs ldx, ldy >= C rounded up to 4.  The kernels move whole 4-element
+ * vectors: x, gamma and beta must be READABLE up to roundup4(C), but what columns [C, roundup4(C)) of x / gamma / beta hold is ignored
+ * (garbage or NaN there changes no result), and columns [C, roundup4(C)) of y are WRITTEN with exact zeros.  Nothing at or past roundup4(C)
+ * is touched. */
 int cs_layernorm_fwd(const void* x, int x_dtype, long ldx, const float* gamma, const float* beta, void* y, long ldy,
                      float* mean, float* rstd, int M, int C, float eps, cs_stream_t stream);
 /* the same, and the e4m3 copy of y for cs_gemm_nt_f8 (precision amp_fp8, src/training/region_clip.py:28-67 under BASELINE configs[4]):
@@ -111,6 +115,9 @@ size_t cs_layernorm_bwd_workspace(int M, int C);
  * dx_copy (modes 1 / 2, nullable): bf16 copy of the dx rows after the write / accumulate (row stride ldcopy) -- the operand of the next
  * dgrad / wgrad GEMMs -- and copy_colsum[C] (nullable) (+)= its column sums = the bias gradient of the linear layer that feeds this
  * residual branch (autograd of x = x + Linear(..) in Block.forward, eva_vit_model.py:306-307): no cast / column-sum pass of their own. */
+/* C % 4 != 0 as in cs_layernorm_fwd (lddy, ldx, lddx, ldcopy >= roundup4(C)): columns [C, roundup4(C)) of dy, x and gamma are read and ignored,
+ * the same columns of dx (mode 2 included: they are overwritten, not accumulated) and dx_copy are written with exact zeros; dgamma, dbeta and
+ * copy_colsum are C long and nothing past C is written.  `workspace` holds cs_layernorm_bwd_workspace(M, C) bytes. */
 int cs_layernorm_bwd(const void* dy, long lddy, const void* x, int x_dtype, long ldx, const float* gamma, const float* mean,
                      const float* rstd, void* dx, int dx_mode, long lddx, float* dgamma, float* dbeta, int accumulate_params,
                      void* workspace, void* dx_copy, long ldcopy, float* copy_colsum, int M, int C, cs_stream_t stream);
@@ -184,7 +191,10 @@ int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R,
 int cs_transpose_bf16_batched(const void* desc, int count, int total_tiles, cs_stream_t stream);
 size_t cs_colsum_workspace(int M, int N);
 int cs_colsum_bf16(const void* x, long ldx, float* out, void* workspace, int M, int N, cs_stream_t stream);   /* out[n] += sum_m x[m,n] (bias grads); fixed summation order, no atomics */
-int cs_im2row(const void* img, int img_dtype, void* out, int B, int S, int p, int ldo, cs_stream_t stream);    /* PatchEmbed unfold, eva_vit_model.py:355 */
+/* PatchEmbed unfold, eva_vit_model.py:355: img [B,3,S,S] f32 / bf16 -> out [B*(S/p)^2, ldo] bf16, row = (c, iy, ix) of one patch.  The WHOLE row
+ * is written: columns [3*p*p, ldo) with zeros (the K padding of the patch GEMM, p = 14: 588 -> 640), so ldo is the row's width, not a stride
+ * past other data. */
+int cs_im2row(const void* img, int img_dtype, void* out, int B, int S, int p, int ldo, cs_stream_t stream);
 int cs_cls_row(float* x, const float* cls, const float* pos, int B, int Ntok, int C, cs_stream_t stream);      /* x[b,0,:] = cls + pos[0], :540-543 */
 
 /* --- RoIAlign 1x1 / aligned / adaptive sampling on the token-major map: torchvision.ops.roi_align called at
@@ -205,7 +215,8 @@ int cs_cosine_loss_bwd(const float* student, const float* teacher, const float* 
 
 /* --- RegionCLIP federated BCE over the sampled noun columns: src/training/region_clip.py:47-56
  *     (F.binary_cross_entropy_with_logits(...).sum(-1).mean() on logits * temp; one-hot target at tgt[k], -1 = none).
- * bwd writes d(logits) as bf16 [K, ldd] with zeroed padding columns (operand of the d(features) GEMM). */
+ * bwd writes d(logits) as bf16 [K, ldd] with zeroed padding columns (operand of the d(features) GEMM): the WHOLE row, columns [ns, ldd)
+ * with zeros, so ldd is the row's width, not a stride past other data. */
 int cs_fed_bce_fwd(const float* logits, long ldz, const int* tgt, float* rowloss, float* loss, int K, int ns, float temp,
                    float weight, cs_stream_t stream);
 int cs_fed_bce_bwd(const float* logits, long ldz, const int* tgt, void* dz_bf16, long ldd, int K, int ns, float temp,
