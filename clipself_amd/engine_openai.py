@@ -1,5 +1,6 @@
-"""Step engine of the OpenAI-CLIP vision transformer on the CLIPSelf hot path: the same flat-buffer
-machinery and kernels as the EVA02 engine (clipself_amd/engine.py), with this tower family's schedule.  Where the reference
+"""Step engine of the OpenAI-CLIP vision transformer on the CLIPSelf hot path: the flat-buffer
+machinery and tower-level drivers of engine_base.TowerEngine and the same kernels as the EVA02 engine, with this tower family's layout, stem,
+block schedule and head.  Where the reference
 does each stage (paths under /root/reference/src/open_clip/):
 
   stem            transformer.py:551-569     conv1 (no bias; im2row + GEMM) + class_embedding + positional_embedding, ln_pre
@@ -13,7 +14,7 @@ does each stage (paths under /root/reference/src/open_clip/):
   lock            transformer.py:391-422     groups = [stem, positional_embedding, blocks..., last block]; the last n train
                                              (n > L: positional_embedding, then conv1 / class_embedding / ln_pre: _stem_bwd)
 
-The frozen teacher uses the EVA02 engine's schedule tricks unchanged: CLS-query-only last block, ln_1 / ln_2 folded into the in_proj / c_fc
+The frozen teacher runs TowerEngine.encode_image like the EVA02 one: CLS-query-only last block, ln_1 / ln_2 folded into the in_proj / c_fc
 GEMMs with the residual GEMMs emitting the bf16 copy and the row statistics of the stream (`_teacher_block_folded`).
 
 Differences to the EVA02 schedule: no RoPE (the attention kernels get identity tables), no sub-LayerNorms, `proj` is a bias-free
@@ -23,11 +24,10 @@ in_proj_weight parameter, whose gradient rows stay zero -- exactly what autograd
 from __future__ import annotations
 
 import torch
-import torch.nn.functional as F
 
 from .config import TowerCfg
-from .engine import (BF16, DX_F32_ACCUM, DX_F32_ASSIGN, EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_PATCH_F32, EPI_QGELU_BF16,
-                     EPI_RESID_F32, F32, EvaEngine, _round_up)
+from .engine_base import (BF16, DX_F32_ACCUM, DX_F32_ASSIGN, EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_PATCH_F32, EPI_QGELU_BF16,
+                          EPI_RESID_F32, F32, TowerEngine, _round_up)
 
 
 def clip_vit_layout(cfg: TowerCfg, prefix: str = "visual."):
@@ -49,19 +49,16 @@ def clip_vit_layout(cfg: TowerCfg, prefix: str = "visual."):
     return groups
 
 
-class ClipVitEngine(EvaEngine):
-    BLOCK_TAG = "transformer.resblocks."
+class ClipVitEngine(TowerEngine):
+    BLOCK_TAG, FINAL_NORM, RESID_BIAS = "transformer.resblocks.", "ln_post", "mlp.c_proj.bias"
+    HEAD_FWD_TRANSPOSED = True                                  # proj^T serves the forward head GEMM of frozen towers too
 
     def __init__(self, cfg: TowerCfg, ops, trainable: bool = False, prefix: str = "visual."):
         if cfg.hidden % 64 or cfg.width % 64 or cfg.embed_dim % 64:
             raise NotImplementedError(f"{cfg.name}: width, MLP width and embed_dim must be multiples of 64")
         super().__init__(cfg, ops, trainable=trainable, prefix=prefix)
-        self.fold_sub_ln = False                                # there are no sub-LayerNorms in this family
-        # Frozen towers, encode_image(): ln_1 / ln_2 are applied inside the in_proj / c_fc GEMM epilogues (gamma folded into a bf16 copy
-        # of the weight, the residual GEMMs emit the bf16 copy of the stream and its row statistics), and the last block runs for the
-        # CLS query only (forward() consumes x[:, 0] alone, transformer.py:486-494).  Same switches as the EVA02 engine.
-        self.fold_block_ln = not trainable
-        self.cls_only_last_block = True
+        # (fold_block_ln here: ln_1 / ln_2 inside the in_proj / c_fc GEMM epilogues; cls_only_last_block: forward() consumes x[:, 0] alone,
+        # transformer.py:486-494)
         self.fold_cls_block = True                              # ln_1 of the CLS-only block folded into its K|V GEMM (A/B switch)
         # lock() with more groups than blocks (transformer.py:391-422): 1 = positional_embedding trains, 2 = conv1 / class_embedding / ln_pre too
         self.stem_level = 0
@@ -69,8 +66,29 @@ class ClipVitEngine(EvaEngine):
     def _layout(self):
         return clip_vit_layout(self.cfg, self.prefix)
 
-    def _never_reached(self, i, name):
-        return False
+    def _pos_table(self, views):
+        return views[self.prefix + "positional_embedding"]
+
+    # ------------------------------------------------------------------------------------------ hooks of the tower drivers
+    def _cls_block_folds(self):
+        return self.fold_cls_block
+
+    def _lo_plane(self, last, cls_folded):
+        return last > 1 or cls_folded
+
+    def _bwd_widths(self):
+        return self.cfg.width, max(self.cfg.hidden, 3 * self.cfg.width)
+
+    def _head(self, rows, out):
+        """out[M,E] f32 = bf16(rows) . proj   (no bias: transformer.py:492-493,583-584)."""
+        self.ops.gemm_nt(rows, self.wt["head_fwd"][:, :self.cfg.width], out, epi=EPI_F32)
+
+    def _head_dgrad(self, d_feats, d_lnf):
+        self.ops.gemm_nt(d_feats, self.w[self.prefix + "proj"], d_lnf, epi=EPI_BF16)      # [M,E] . proj^T: proj [C,E] is already "W^T"
+
+    def _head_wgrad(self, d_feats, lnf, ws):
+        """dproj [C,E] = LN(x)^T . dfeats   (transformer.py:583-584: tokens @ proj; no bias)."""
+        self._wgrad(lnf, d_feats, self.g[self.prefix + "proj"])
 
     # ------------------------------------------------------------------------------------------ parameters
     def sync_transposed(self, blocks=None):
@@ -85,14 +103,6 @@ class ClipVitEngine(EvaEngine):
                 pairs.append((self.w[b + "mlp.c_fc.weight"], self._wt_alloc((i, "fc"), Hd, C)))
                 pairs.append((self.w[b + "mlp.c_proj.weight"], self._wt_alloc((i, "cproj"), C, Hd)))
         self.ops.transpose_bf16_batched(pairs)
-
-    def sync_shadow(self):
-        self.ops.cast_f32_bf16(self.master, self.shadow)
-        self._pos_cache.clear()
-        self.block_fold_ratio = None
-        self.sync_transposed()
-        if self.fold_block_ln:
-            self._build_folds()
 
     def _build_folds(self):
         """gamma (.) W in bf16, its row sums and W.beta + b for ln_1 -> in_proj and ln_2 -> c_fc of every block (one-time, after a load)."""
@@ -144,18 +154,6 @@ class ClipVitEngine(EvaEngine):
             shape = (grid * grid, self.cfg.head_width)
             self._tables[key] = (torch.ones(shape, dtype=F32, device=self.device), torch.zeros(shape, dtype=F32, device=self.device))
         return self._tables[key]
-
-    def pos_for(self, grid: int):
-        """positional_embedding [N, C] fp32, bicubic-rescaled for a non-native grid (transformer.py:724-734); cached per grid."""
-        if grid not in self._pos_cache:
-            pe = self.p[self.prefix + "positional_embedding"]
-            if grid != self.cfg.grid:
-                C = pe.shape[1]
-                pe2 = pe[1:].T.contiguous().view(1, C, self.cfg.grid, self.cfg.grid)
-                pe2 = F.interpolate(pe2, (grid, grid), mode="bicubic", align_corners=False).view(C, grid * grid)
-                pe = torch.cat([pe[:1], pe2.T], dim=0)
-            self._pos_cache[grid] = pe.contiguous()
-        return self._pos_cache[grid]
 
     # ------------------------------------------------------------------------------------------ forward pieces
     def _stem(self, images, keep=None):
@@ -226,8 +224,8 @@ class ClipVitEngine(EvaEngine):
         """One frozen-tower block with both LayerNorms folded into the GEMMs (in place on x).  xb / st = bf16 copy and (mean, rstd) of x as
         left by the previous block's c_proj GEMM, or None (first block: plain ln_1 kernel).  Returns (xb, st) for the next block when
         emit_next.  With lo (int16 [M, C]; round 4) the stream lives in the two 16-bit planes (xb, lo) between the first residual GEMM of
-        the tower, which reads fp32 x, and the last one (emit_next False), which writes fp32 x again -- cs_gemm_nt_ln_split as in the EVA02
-        engine: 8 instead of 10 bytes per stream element and residual GEMM, same fp32 values.  This family has no LayerNorm in front of
+        the tower, which reads fp32 x, and the last one (emit_next False), which writes fp32 x again -- cs_gemm_nt_ln_split:
+        8 instead of 10 bytes per stream element and residual GEMM, same fp32 values.  This family has no LayerNorm in front of
         out_proj / c_proj, so the split kernel gets the identity statistics (mean 0, rstd 1, column sums 0: x + 1 * (acc - 0 * 0) + b)."""
         ops, cfg = self.ops, self.cfg
         C, Hd, H, eps = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps
@@ -284,7 +282,7 @@ class ClipVitEngine(EvaEngine):
         """Last teacher block restricted to what forward() consumes: the CLS row.  x fp32 [B*N, C] -> fp32 [B, C]; keys and values still
         come from every token.  Row-for-row the same arithmetic as _block_fwd.  With xb / st (/ lo) -- the bf16 operand view, ln_1 statistics
         (and low plane) the previous folded block left -- ln_1 is folded into the K|V GEMM like in every other block (no LayerNorm pass over
-        the whole stream, which never returns to fp32) and only the B CLS rows are rebuilt in fp32 (EvaEngine._block_fwd_cls)."""
+        the whole stream, which never returns to fp32) and only the B CLS rows are rebuilt in fp32."""
         ops, cfg = self.ops, self.cfg
         C, Hd, H, eps = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps
         b = f"{self.prefix}{self.BLOCK_TAG}{i}."
@@ -315,46 +313,6 @@ class ClipVitEngine(EvaEngine):
         ops.gemm_nt(ln2, self.w[b + "mlp.c_fc.weight"], hid, bias=self.p[b + "mlp.c_fc.bias"], epi=EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16)
         ops.gemm_nt(hid, self.w[b + "mlp.c_proj.weight"], xc, bias=self.p[b + "mlp.c_proj.bias"], extra=xc, epi=EPI_RESID_F32)
         return xc
-
-    def _head(self, rows, out):
-        """out[M,E] f32 = bf16(rows) . proj   (no bias: transformer.py:492-493,583-584)."""
-        self.ops.gemm_nt(rows, self.wt["head_fwd"][:, :self.cfg.width], out, epi=EPI_F32)
-
-    # ------------------------------------------------------------------------------------------ teacher
-    def encode_image(self, images, chunk: int = 256):
-        """Frozen-teacher path: every block with attention, ln_post on the CLS row, proj.  [K,3,S,S] -> fp32 [K,E]."""
-        ops, cfg, P = self.ops, self.cfg, self.prefix
-        K = images.shape[0]
-        out = ops.empty((K, cfg.embed_dim), F32)
-        fold_blocks = self.block_folds_active(images)          # the switch + the row-statistics guard of the current weights (EvaEngine)
-        for k0 in range(0, K, chunk):
-            img = images[k0:k0 + chunk]
-            B = img.shape[0]
-            x, g = self._stem(img)
-            N = g * g + 1
-            cos, sin = self.rope_tables(g)
-            xf = x.view(B * N, cfg.width)
-            last = cfg.layers - 1 if self.cls_only_last_block else cfg.layers
-            xb = st = None
-            cls_folded = fold_blocks and self.fold_cls_block and last < cfg.layers and last > 0      # the CLS-only block takes the planes + statistics as they are
-            lo = ops.empty((B * N, cfg.width), torch.int16) if fold_blocks and self.split_stream and (last > 1 or cls_folded) else None
-            try:
-                for i in range(last):
-                    self._rccl_window_step(i, k0)                # EvaEngine: leading blocks of a prefetched pass leave CUs to RCCL
-                    if fold_blocks:
-                        xb, st = self._teacher_block_folded(i, xf, xb, st, B, N, cos, sin, emit_next=i + 1 < last or cls_folded, lo=lo)
-                    else:
-                        self._block_fwd(i, xf, B, N, cos, sin, True, None, True)
-            finally:
-                self._rccl_window_close(k0)
-            if last < cfg.layers:
-                xc = self._block_fwd_cls(last, xf, B, N, cos, sin, xb if cls_folded else None, st, lo)
-            else:
-                xc = x[:, 0, :]
-            cls = ops.empty((B, cfg.width), BF16)
-            ops.layernorm_fwd(xc, self.p[P + "ln_post.weight"], self.p[P + "ln_post.bias"], cls, None, None, cfg.ln_eps)
-            self._head(cls, out[k0:k0 + B])
-        return out
 
     # ------------------------------------------------------------------------------------------ mask-attention pooling (inference)
     def mask_attn_pool(self, images, masks, chunk: int = 64):
@@ -424,41 +382,11 @@ class ClipVitEngine(EvaEngine):
             outs += [pooled[b, :n] for b, n in enumerate(counts[k0:k0 + B])]
         return torch.cat(outs)
 
-    # ------------------------------------------------------------------------------------------ student
-    def encode_dense(self, images, need_grad: bool = False):
-        ops, cfg, P = self.ops, self.cfg, self.prefix
-        B = images.shape[0]
-        stem_keep = {} if (need_grad and self.stem_level > 0) else None
-        x, g = self._stem(images, stem_keep)
-        N, C, E = g * g + 1, cfg.width, cfg.embed_dim
-        cos, sin = self.rope_tables(g)
-        xf = x.view(B * N, C)
-        saves = {}
-        for i in range(cfg.layers):
-            keep = need_grad and i >= self.first_trainable
-            save = {} if keep else None
-            xf = self._block_fwd(i, xf, B, N, cos, sin, with_attn=(i < cfg.layers - 1), save=save, inplace=not keep)
-            if keep:
-                saves[i] = save
-        M = B * N
-        lnf = ops.empty((M, C), BF16)
-        mean = ops.empty((M,), F32) if need_grad else None
-        rstd = ops.empty((M,), F32) if need_grad else None
-        ops.layernorm_fwd(xf, self.p[P + "ln_post.weight"], self.p[P + "ln_post.bias"], lnf, mean, rstd, cfg.ln_eps)
-        feats = ops.empty((M, E), F32)
-        self._head(lnf, feats)
-        dense = ops.empty((M, E), F32)
-        inv = ops.empty((M,), F32)
-        ops.l2norm_fwd(feats, dense, inv)
-        if need_grad:
-            self._ctx = dict(B=B, N=N, g=g, saves=saves, xL=xf, stf=(mean, rstd), dense=dense, inv=inv, cos=cos, sin=sin, stem=stem_keep,
-                             lnf=lnf if self.train_all else None)
-        return dense.view(B, N, E), g
-
     # ------------------------------------------------------------------------------------------ backward
-    def _block_bwd(self, i, s, g, gb, B, N, cos, sin, ws, next_bias=None):
-        """g: fp32 [M,C] gradient w.r.t. the block output; updated in place to the gradient w.r.t. its input.  gb / next_bias: as in
-        EvaEngine._block_bwd (the bf16 copy of g and its column sums come out of the LayerNorm backwards)."""
+    def _block_bwd(self, i, s, g, gb, B, N, cos, sin, ws, next_bias=None, gq=None):
+        """g: fp32 [M,C] gradient w.r.t. the block output; updated in place to the gradient w.r.t. its input.  gb: its bf16 copy, already summed
+        into this block's c_proj bias gradient by the LayerNorm backward that produced it; on return gb is the copy of the new g and its column
+        sums have gone to `next_bias` (block i-1's c_proj bias gradient, or None).  gq: always None here (no fp8 dgrad in this family)."""
         ops, cfg = self.ops, self.cfg
         C, Hd, H = cfg.width, cfg.hidden, cfg.heads
         b = f"{self.prefix}{self.BLOCK_TAG}{i}."
@@ -496,48 +424,10 @@ class ClipVitEngine(EvaEngine):
                           G[b + "ln_1.weight"], G[b + "ln_1.bias"], True, ws[0], dx_copy=gb if next_bias is not None else None,
                           copy_colsum=next_bias)
 
-    def backward_dense(self, d_dense):
-        ops, cfg, P = self.ops, self.cfg, self.prefix
-        c = self._ctx
-        if c is None:
-            raise RuntimeError("backward_dense() without a preceding encode_dense(need_grad=True)")
-        self._ctx = None
-        B, N, C, E = c["B"], c["N"], cfg.width, cfg.embed_dim
-        M = B * N
-        d_feats = ops.empty((M, E), BF16)
-        ops.l2norm_bwd(d_dense.reshape(M, E), c["dense"], c["inv"], d_feats)
-        d_lnf = ops.empty((M, C), BF16)
-        ops.gemm_nt(d_feats, self.w[P + "proj"], d_lnf, epi=EPI_BF16)                        # [M,E] . proj^T: proj [C,E] is already "W^T"; frozen
-        g = ops.empty((M, C), F32)
-        gb = ops.empty((M, C), BF16)
-        ws_bytes = max(ops.layernorm_bwd_workspace(M, C), ops.attn_bwd_workspace(B, N, cfg.heads))
-        ws = (ops.empty((ws_bytes,), torch.uint8), ops.empty((max(ops.colsum_workspace(M, max(cfg.hidden, 3 * C)), 4),), torch.uint8))
-        L, first = cfg.layers, self.first_trainable
-        cproj_bias = lambda i: self.g[f"{P}{self.BLOCK_TAG}{i}.mlp.c_proj.bias"] if i >= first else None
-        if self.train_all:
-            # proj [C,E] (transformer.py:583-584: tokens @ proj) and ln_post train: dproj = LN(x)^T . dfeats; the CLS rows of d_feats are exact
-            # zeros (the dense map drops them), so they add nothing
-            self._wgrad(c["lnf"], d_feats, self.g[P + "proj"])
-            ops.layernorm_bwd(d_lnf, c["xL"], self.p[P + "ln_post.weight"], *c["stf"], g, DX_F32_ASSIGN, self.g[P + "ln_post.weight"],
-                              self.g[P + "ln_post.bias"], True, ws[0], dx_copy=gb, copy_colsum=cproj_bias(L - 1))
-            if self.grad_ready_hook is not None:
-                self.grad_ready_hook("head")
-        else:
-            ops.layernorm_bwd(d_lnf, c["xL"], self.p[P + "ln_post.weight"], *c["stf"], g, DX_F32_ASSIGN, None, None, True, ws[0],   # ln_post frozen
-                              dx_copy=gb if first < L else None, copy_colsum=cproj_bias(L - 1))                                    # (transformer.py:405)
-        for i in range(L - 1, first - 1, -1):
-            self._block_bwd(i, c["saves"].pop(i), g, gb, B, N, c["cos"], c["sin"], ws, next_bias=cproj_bias(i - 1) if i > 0 else None)
-            if self.grad_ready_hook is not None:
-                self.grad_ready_hook(i)
-        if c["stem"] is not None:
-            self._stem_bwd(g, c["stem"], B, N, c["g"], ws[0])
-            if self.grad_ready_hook is not None:
-                self.grad_ready_hook("stem")
-
     def _stem_bwd(self, g, keep, B, N, grid, ws):
         """Gradients of the stem from g = d loss / d (ln_pre output) fp32 [B*N, C]  (transformer.py:551-569: x = ln_pre(cat(class_embedding,
         conv1(img)) + positional_embedding)).  ln_pre backward (its gamma / beta at stem level 2), then: positional_embedding <- sum over images
-        (through the bicubic rescale for a non-native grid, :724-734), class_embedding <- the CLS rows, conv1.weight <- dY^T . im2row(images) (no
+        (_pos_grad), class_embedding <- the CLS rows, conv1.weight <- dY^T . im2row(images) (no
         bias).  Once per step on [B*N, C]; the row bookkeeping is tensor code, the LayerNorm backward and the contraction are the kernels."""
         ops, cfg, P = self.ops, self.cfg, self.prefix
         C, M = cfg.width, B * N
@@ -547,16 +437,7 @@ class ClipVitEngine(EvaEngine):
                           self.g[P + "ln_pre.weight"] if lvl2 else None, self.g[P + "ln_pre.bias"] if lvl2 else None, True, ws)
         d3 = d_pre.view(B, N, C)
         d_pos = d3.sum(dim=0)                                                    # [N, C]
-        gpos = self.g[P + "positional_embedding"]                                # [native N, C]
-        if grid == cfg.grid:
-            gpos.add_(d_pos)
-        else:
-            gpos[0].add_(d_pos[0])
-            with torch.enable_grad():
-                pe = self.p[P + "positional_embedding"].detach()[1:].T.reshape(1, C, cfg.grid, cfg.grid).clone().requires_grad_(True)
-                out = F.interpolate(pe, (grid, grid), mode="bicubic", align_corners=False)
-                (d_pe,) = torch.autograd.grad(out, pe, d_pos[1:].T.reshape(1, C, grid, grid))
-            gpos[1:].add_(d_pe.reshape(C, cfg.grid * cfg.grid).T)
+        self._pos_grad(d_pos, grid)
         if lvl2:
             self.g[P + "class_embedding"].view(C).add_(d_pos[0])
             gp = d3[:, 1:, :].to(BF16).reshape(B * (N - 1), C)                   # patch rows, in the im2row matrix's row order
