@@ -1075,7 +1075,7 @@ template <int HG>
 __global__ __launch_bounds__(256) void attn_cls_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ kv,
                                                        const float* __restrict__ cos_t, const float* __restrict__ sin_t,
                                                        __bf16* __restrict__ out, int Ntok, int H, int ldq, int ldkv, int ldo, float scale,
-                                                       int qpb, const unsigned char* __restrict__ allow) {
+                                                       int qpb, const unsigned char* __restrict__ allow, float* __restrict__ lse_out) {
     extern __shared__ float sm[];                 // [HG][Npad] scores -> probabilities | [HG] row sums | [4 waves][HG*64] partial outputs
     const int Npad = (Ntok + 3) & ~3;
     float* rsum = sm + HG * Npad;
@@ -1122,7 +1122,8 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const __bf16* __restrict_
         float mx = -INFINITY;
         for (int key = lane; key < Ntok; key += 64) mx = fmaxf(mx, row[key]);
         mx = wave_max(mx);
-        if (mx == -INFINITY) mx = 0.f;             // a query row that allows no key at all (the reference always allows key 0): p = 0 everywhere,
+        const bool no_key = mx == -INFINITY;
+        if (no_key) mx = 0.f;                      // a query row that allows no key at all (the reference always allows key 0): p = 0 everywhere,
         float sum = 0.f;                           // output row = 0 instead of exp2(-inf + inf) = NaN
         for (int key = lane; key < Ntok; key += 64) {
             const float e = __builtin_amdgcn_exp2f(row[key] - mx);
@@ -1131,6 +1132,9 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const __bf16* __restrict_
         }
         sum = wave_sum(sum);
         if (lane == 0) rsum[h] = sum > 0.f ? sum : 1.f;
+        // natural log-sum-exp of the scaled scores over the allowed keys, [B*H, qpb]; +inf for a row without keys (p = 0 in the backward)
+        if (lane == 0 && lse_out)
+            lse_out[((size_t)(b / qpb) * H + h0 + h) * qpb + b % qpb] = no_key ? INFINITY : (mx + __builtin_log2f(sum)) * (1.f / LOG2E);
     }
     __syncthreads();
     float acc[HG][8];
@@ -1166,6 +1170,172 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const __bf16* __restrict_
         const float v = (part[o] + part[HG * HD + o]) + (part[2 * HG * HD + o] + part[3 * HG * HD + o]);
         out[(size_t)b * ldo + h0 * HD + o] = f2bf(v / rsum[o / HD]);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ passenger backward
+// Backward of cs_attn_query_fwd's extra query rows ("passengers": open_clip/transformer.py:736-834 under autograd).  Latency class: one
+// streaming pass over K|V.  A workgroup owns PKB keys of one (image, head) -- 8 lanes per key, 16 bytes of the head dim each, two keys per
+// thread -- and sweeps all Q passengers of the image in tiles of PQT rows staged in LDS (q, dO, their row constants and allow bytes), so the passengers' dK / dV of its keys are complete
+// in registers when the sweep ends: they are added to the k|v columns of dqkv once (bf16 read, fp32 add, one rounding), after the image
+// tokens' kernels of the same call, or written as they are when the launch has no image rows.  dq_r is a sum over key blocks: every
+// workgroup leaves its fp32 partial in the workspace and attn_pass_dq_kernel adds them in key-block order -- no atomics, bit-reproducible.
+// Rounding points are those of the image kernels: p and dS rounded to bf16 before the dV / dK / dQ products, fp32 sums.
+constexpr int PKB = 64, PQT = 32;
+
+struct PassArgs {
+    const __bf16* qkv;             // [B*Ntok, ldqkv]: the k | v columns are read
+    const __bf16* q;               // [B*Q, ldq]
+    const __bf16* o;               // [B*Q, ldo]
+    const __bf16* dout;            // [B*Q, ldo]
+    const float* lse;              // [B*H, Q]
+    const unsigned char* allow;    // [B*Q, Ntok]
+    __bf16* dqkv;                  // [B*Ntok, ldqkv]
+    float* part;                   // [B*H][nkb][Q][64]
+    __bf16* dq;                    // [B*Q, lddq]
+    int Ntok, H, Q, ldqkv, ldq, ldo, lddq, nkb, assign;
+    float scale;
+};
+
+__global__ __launch_bounds__(256) void attn_pass_bwd_kernel(PassArgs p) {
+    __shared__ float sq[PQT][HD];
+    __shared__ float sdo[PQT][HD];
+    __shared__ float sds[PQT][PKB + 1];
+    __shared__ __bf16 sk[PKB][HD + 8];
+    __shared__ float srow[2][PQT];                 // -lse * log2(e) | D = sum dO . O
+    __shared__ unsigned char sal[PQT][PKB];        // allow bytes of the (passenger tile, key block); 0 past Q / Ntok
+    const int tid = threadIdx.x, c = tid & 7, kg = tid >> 3;
+    const int kb = blockIdx.x, bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
+    const int C = p.H * HD, key0 = kb * PKB;
+    float kf[2][8], vf[2][8], dk[2][8], dv[2][8];
+    bool live[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int key = key0 + kg + 32 * t;
+        live[t] = key < p.Ntok;
+        U128 kk, vv;
+        kk.u = make_uint4(0, 0, 0, 0);
+        vv.u = kk.u;
+        if (live[t]) {
+            const __bf16* src = p.qkv + ((size_t)b * p.Ntok + key) * p.ldqkv + C + h * HD + c * 8;
+            kk.u = *(const uint4*)src;
+            vv.u = *(const uint4*)(src + C);
+        }
+        *(uint4*)&sk[kg + 32 * t][c * 8] = kk.u;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { kf[t][j] = bf2f(kk.e[j]); vf[t][j] = bf2f(vv.e[j]); dk[t][j] = 0.f; dv[t][j] = 0.f; }
+    }
+    const float sl2 = p.scale * LOG2E;
+    for (int r0 = 0; r0 < p.Q; r0 += PQT) {
+        __syncthreads();                           // the previous tile's dQ pass has read sds
+        {
+            const int r = r0 + kg;                 // staging: 8 lanes per passenger row
+            float qv[8], dov[8], dsum = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { qv[j] = 0.f; dov[j] = 0.f; }
+            if (r < p.Q) {
+                const size_t row = (size_t)b * p.Q + r;
+                U128 a, d, oo;
+                a.u = *(const uint4*)(p.q + row * p.ldq + h * HD + c * 8);
+                d.u = *(const uint4*)(p.dout + row * p.ldo + h * HD + c * 8);
+                oo.u = *(const uint4*)(p.o + row * p.ldo + h * HD + c * 8);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { qv[j] = bf2f(a.e[j]); dov[j] = bf2f(d.e[j]); dsum += dov[j] * bf2f(oo.e[j]); }
+            }
+            dsum = sum_lanes8(dsum);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { sq[kg][c * 8 + j] = qv[j]; sdo[kg][c * 8 + j] = dov[j]; }
+            if (c == 0) {
+                srow[0][kg] = r < p.Q ? -p.lse[(size_t)bh * p.Q + r] * LOG2E : -INFINITY;
+                srow[1][kg] = dsum;
+            }
+        }
+        for (int i = tid; i < PQT * PKB; i += 256) {
+            const int rl = i / PKB, kk = i - rl * PKB, r = r0 + rl, key = key0 + kk;
+            sal[rl][kk] = (r < p.Q && key < p.Ntok) ? p.allow[((size_t)b * p.Q + r) * p.Ntok + key] : (unsigned char)0;
+        }
+        __syncthreads();
+        const int nr = min(PQT, p.Q - r0);
+        for (int rl = 0; rl < nr; ++rl) {
+            float qv[8], dov[8];
+            {
+                const float4 a0 = *(const float4*)&sq[rl][c * 8], a1 = *(const float4*)&sq[rl][c * 8 + 4];
+                const float4 d0 = *(const float4*)&sdo[rl][c * 8], d1 = *(const float4*)&sdo[rl][c * 8 + 4];
+                qv[0] = a0.x; qv[1] = a0.y; qv[2] = a0.z; qv[3] = a0.w; qv[4] = a1.x; qv[5] = a1.y; qv[6] = a1.z; qv[7] = a1.w;
+                dov[0] = d0.x; dov[1] = d0.y; dov[2] = d0.z; dov[3] = d0.w; dov[4] = d1.x; dov[5] = d1.y; dov[6] = d1.z; dov[7] = d1.w;
+            }
+            const float nl = srow[0][rl], dsum = srow[1][rl];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                float s = 0.f, dp = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { s += qv[j] * kf[t][j]; dp += dov[j] * vf[t][j]; }
+                s = sum_lanes8(s);
+                dp = sum_lanes8(dp);
+                const bool ok = sal[rl][kg + 32 * t] != 0;
+                const float pr = ok ? __builtin_amdgcn_exp2f(__builtin_fmaf(s, sl2, nl)) : 0.f;
+                const float ds = bf2f(f2bf(pr * (dp - dsum) * p.scale));
+                const float pb = bf2f(f2bf(pr));
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { dk[t][j] += ds * qv[j]; dv[t][j] += pb * dov[j]; }
+                if (c == 0) sds[rl][kg + 32 * t] = ds;
+            }
+        }
+        __syncthreads();
+        if (kg < nr) {                             // dQ partial of this key block: 8 lanes per passenger row, 8 head dims each
+            float acc[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+            for (int key = 0; key < PKB; ++key) {
+                U128 kk;
+                kk.u = *(const uint4*)&sk[key][c * 8];
+                const float ds = sds[kg][key];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] += ds * bf2f(kk.e[j]);
+            }
+            float* dst = p.part + (((size_t)bh * p.nkb + kb) * p.Q + r0 + kg) * HD + c * 8;
+            *(float4*)dst = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            *(float4*)(dst + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        if (!live[t]) continue;
+        __bf16* row = p.dqkv + ((size_t)b * p.Ntok + key0 + kg + 32 * t) * p.ldqkv + h * HD + c * 8;
+        U128 ok_, ov;
+        if (p.assign) {                            // no image rows in this launch: dqkv = [0 | passenger dK | passenger dV]
+            *(uint4*)row = make_uint4(0, 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { ok_.e[j] = f2bf(dk[t][j]); ov.e[j] = f2bf(dv[t][j]); }
+        } else {
+            ok_.u = *(const uint4*)(row + C);
+            ov.u = *(const uint4*)(row + 2 * C);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { ok_.e[j] = f2bf(bf2f(ok_.e[j]) + dk[t][j]); ov.e[j] = f2bf(bf2f(ov.e[j]) + dv[t][j]); }
+        }
+        *(uint4*)(row + C) = ok_.u;
+        *(uint4*)(row + 2 * C) = ov.u;
+    }
+}
+
+// dq [B*Q, lddq] bf16 = the key blocks' fp32 partials added in key-block order
+__global__ __launch_bounds__(256) void attn_pass_dq_kernel(PassArgs p, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i & 7);
+    const long rr = i >> 3;                        // bh * Q + r
+    const int r = (int)(rr % p.Q), bh = (int)(rr / p.Q), b = bh / p.H, h = bh - b * p.H;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    for (int kb = 0; kb < p.nkb; ++kb) {
+        const float* src = p.part + (((size_t)bh * p.nkb + kb) * p.Q + r) * HD + c * 8;
+        const float4 a0 = *(const float4*)src, a1 = *(const float4*)(src + 4);
+        acc[0] += a0.x; acc[1] += a0.y; acc[2] += a0.z; acc[3] += a0.w; acc[4] += a1.x; acc[5] += a1.y; acc[6] += a1.z; acc[7] += a1.w;
+    }
+    U128 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out.e[j] = f2bf(acc[j]);
+    *(uint4*)(p.dq + ((size_t)b * p.Q + r) * p.lddq + h * HD + c * 8) = out.u;
 }
 
 }  // namespace
@@ -1226,14 +1396,29 @@ extern "C" int cs_attn_fwd_stats(const void* qkv, const float* cos_t, const floa
 
 // dsum [B*H, Ntok] f32, and for sequences of more than one key chunk the rotated q | k of the launch ([B*Ntok, 2C] bf16, 256-byte aligned)
 static size_t bwd_dsum_bytes(int B, int Ntok, int H) { return (((size_t)B * H * Ntok * sizeof(float)) + 255) & ~(size_t)255; }
-extern "C" size_t cs_attn_bwd_workspace(int B, int Ntok, int H) {
+static size_t bwd_image_bytes(int B, int Ntok, int H) {
     return bwd_dsum_bytes(B, Ntok, H) + (Ntok > 7 * 32 ? (size_t)B * Ntok * 2 * H * HD * sizeof(__bf16) : 0);
 }
+// ... and, with Q extra query rows per image (cs_attn_bwd's `extra`), their dq partials: [B*H][key blocks][Q][64] f32, 256-byte aligned
+extern "C" size_t cs_attn_bwd_workspace(int B, int Ntok, int H, int Q) {
+    const size_t img = bwd_image_bytes(B, Ntok, H);
+    if (Q <= 0) return img;
+    return ((img + 255) & ~(size_t)255) + (size_t)B * H * ((Ntok + PKB - 1) / PKB) * Q * HD * sizeof(float);
+}
 
-// o, dout [B*N, ldo] bf16; lse from the forward; dqkv [B*N, ldqkv] bf16 receives d(q|k|v) w.r.t. the *un-rotated* q,k.
-extern "C" int cs_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, const float* cos_t, const float* sin_t,
-                           void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, hipStream_t stream) {
-    if (check_common("cs_attn_bwd", B, Ntok, H, ldqkv, ldo)) return -1;
+// C-side mirror of include/clipself_hip.h's cs_attn_extra
+struct cs_attn_extra {
+    const void* q;
+    const void* o;
+    const void* dout;
+    const float* lse;
+    const unsigned char* allow;
+    void* dq;
+    int Q, ldq, ldo, lddq;
+};
+
+static int attn_bwd_image(const void* qkv, const void* o, const void* dout, const float* lse, const float* cos_t, const float* sin_t,
+                          void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, hipStream_t stream) {
     CS_CHECK_ARG(workspace != nullptr && lse != nullptr, "cs_attn_bwd: workspace and lse are required");
     float* dsum = (float*)workspace;
     const long total = (long)B * Ntok * H * 8;
@@ -1289,8 +1474,40 @@ extern "C" int cs_attn_bwd(const void* qkv, const void* o, const void* dout, con
     return 0;
 }
 
+// o, dout [B*N, ldo] bf16; lse from the forward; dqkv [B*N, ldqkv] bf16 receives d(q|k|v) w.r.t. the *un-rotated* q,k.
+// extra (nullable): the Q extra query rows per image of cs_attn_query_fwd.  Their dK / dV are added to the k|v columns of dqkv after the image
+// rows' kernels, their dq goes to extra->dq; with extra, o / dout / lse may all be NULL (no image rows: dqkv = [0 | dK | dV]).
+extern "C" int cs_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, const float* cos_t, const float* sin_t,
+                           void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, const cs_attn_extra* extra,
+                           hipStream_t stream) {
+    if (check_common("cs_attn_bwd", B, Ntok, H, ldqkv, ldo)) return -1;
+    if (extra == nullptr) return attn_bwd_image(qkv, o, dout, lse, cos_t, sin_t, dqkv, workspace, B, Ntok, H, ldqkv, ldo, scale, stream);
+    const cs_attn_extra& e = *extra;
+    const bool image = o != nullptr || dout != nullptr || lse != nullptr;
+    CS_CHECK_ARG(qkv && dqkv && workspace, "cs_attn_bwd: qkv, dqkv and workspace are required");
+    CS_CHECK_ARG(!image || (o && dout && lse), "cs_attn_bwd: with extra rows, o / dout / lse of the image rows are given together or not at all");
+    CS_CHECK_ARG(e.q && e.o && e.dout && e.lse && e.allow && e.dq && e.Q > 0, "cs_attn_bwd: extra rows: null pointer or Q=%d", e.Q);
+    CS_CHECK_ARG(e.ldq % 8 == 0 && e.ldo % 8 == 0 && e.lddq % 8 == 0 && e.ldq >= H * HD && e.ldo >= H * HD && e.lddq >= H * HD,
+                 "cs_attn_bwd: extra rows: row strides must be multiples of 8 and cover the heads (ldq=%d ldo=%d lddq=%d)", e.ldq, e.ldo, e.lddq);
+    CS_CHECK_ARG(((uintptr_t)e.q % 16) == 0 && ((uintptr_t)e.o % 16) == 0 && ((uintptr_t)e.dout % 16) == 0 && ((uintptr_t)e.dq % 16) == 0 &&
+                 ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)dqkv % 16) == 0, "cs_attn_bwd: extra rows: buffers must be 16-byte aligned");
+    if (image && attn_bwd_image(qkv, o, dout, lse, cos_t, sin_t, dqkv, workspace, B, Ntok, H, ldqkv, ldo, scale, stream)) return -1;
+    PassArgs p{};
+    p.qkv = (const __bf16*)qkv; p.q = (const __bf16*)e.q; p.o = (const __bf16*)e.o; p.dout = (const __bf16*)e.dout; p.lse = e.lse;
+    p.allow = e.allow; p.dqkv = (__bf16*)dqkv; p.dq = (__bf16*)e.dq;
+    p.part = (float*)((char*)workspace + ((bwd_image_bytes(B, Ntok, H) + 255) & ~(size_t)255));
+    p.Ntok = Ntok; p.H = H; p.Q = e.Q; p.ldqkv = ldqkv; p.ldq = e.ldq; p.ldo = e.ldo; p.lddq = e.lddq;
+    p.nkb = (Ntok + PKB - 1) / PKB; p.assign = image ? 0 : 1; p.scale = scale;
+    hipLaunchKernelGGL(attn_pass_bwd_kernel, dim3(p.nkb, B * H), dim3(256), 0, stream, p);
+    CS_LAUNCH_CHECK();
+    const long total = (long)B * H * e.Q * 8;
+    hipLaunchKernelGGL(attn_pass_dq_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, total);
+    CS_LAUNCH_CHECK();
+    return 0;
+}
+
 static int attn_cls_launch(const void* q, const void* kv, const float* cos_t, const float* sin_t, void* out, int rows, int Ntok, int H,
-                           int ldq, int ldkv, int ldo, float scale, int qpb, const unsigned char* allow, hipStream_t stream) {
+                           int ldq, int ldkv, int ldo, float scale, int qpb, const unsigned char* allow, float* lse, hipStream_t stream) {
     const int HG = H % 6 == 0 ? 6 : (H % 4 == 0 ? 4 : (H % 3 == 0 ? 3 : (H % 2 == 0 ? 2 : 1)));
     const size_t lds = ((size_t)HG * ((Ntok + 3) & ~3) + 8 + (size_t)4 * HG * HD) * sizeof(float);
     CS_CHECK_ARG(lds <= 160 * 1024, "cs_attn_cls_fwd: Ntok=%d too large", Ntok);
@@ -1300,7 +1517,7 @@ static int attn_cls_launch(const void* q, const void* kv, const float* cos_t, co
         static bool once = (set_lds(attn_cls_kernel<G>, 160 * 1024), true);                                                   \
         (void)once;                                                                                                           \
         hipLaunchKernelGGL(attn_cls_kernel<G>, grid, block, lds, stream, (const __bf16*)q, (const __bf16*)kv, cos_t, sin_t,   \
-                           (__bf16*)out, Ntok, H, ldq, ldkv, ldo, scale, qpb, allow);                                         \
+                           (__bf16*)out, Ntok, H, ldq, ldkv, ldo, scale, qpb, allow, lse);                                      \
     }
     switch (HG) {
         case 6: CS_CLS_LAUNCH(6) break;
@@ -1323,19 +1540,20 @@ extern "C" int cs_attn_cls_fwd(const void* q, const void* kv, const float* cos_t
     CS_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldq >= H * HD && ldkv >= 2 * H * HD && ldo >= H * HD,
                  "cs_attn_cls_fwd: row strides must be multiples of 8 and cover the heads (ldq=%d ldkv=%d ldo=%d)", ldq, ldkv, ldo);
     CS_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)kv % 16) == 0, "cs_attn_cls_fwd: q/kv must be 16-byte aligned");
-    return attn_cls_launch(q, kv, cos_t, sin_t, out, B, Ntok, H, ldq, ldkv, ldo, scale, 1, nullptr, stream);
+    return attn_cls_launch(q, kv, cos_t, sin_t, out, B, Ntok, H, ldq, ldkv, ldo, scale, 1, nullptr, nullptr, stream);
 }
 
 // Extra query tokens of the OpenAI-CLIP family's mask-attention pooling (open_clip/transformer.py:736-834, reached through
 // extract_type='v1' :660-671 and encode_masks(mask_attn=True), model.py:245-247): Q query rows per image against the image's own keys /
 // values of the same depth, key j of query row r allowed iff allow[r * Ntok + j] != 0 (key 0 = the CLS token, always allowed there).
-// q [B*Q, ldq] bf16; kv [B*Ntok, ldkv] bf16 = k|v; out [B*Q, ldo] bf16.  No rotary embedding in this family.  Inference only.
-extern "C" int cs_attn_query_fwd(const void* q, const void* kv, const unsigned char* allow, void* out, int B, int Q, int Ntok, int H,
+// q [B*Q, ldq] bf16; kv [B*Ntok, ldkv] bf16 = k|v; out [B*Q, ldo] bf16.  No rotary embedding in this family.  lse (nullable) [B*H, Q] f32:
+// the natural log-sum-exp of the scaled scores over a row's allowed keys (+inf for a row that allows none), for cs_attn_bwd's `extra`.
+extern "C" int cs_attn_query_fwd(const void* q, const void* kv, const unsigned char* allow, void* out, float* lse, int B, int Q, int Ntok, int H,
                                  int ldq, int ldkv, int ldo, float scale, hipStream_t stream) {
     CS_CHECK_ARG(q && kv && allow && out, "cs_attn_query_fwd: null pointer");
     CS_CHECK_ARG(B > 0 && Q > 0 && Ntok > 1 && H > 0, "cs_attn_query_fwd: bad sizes B=%d Q=%d Ntok=%d H=%d", B, Q, Ntok, H);
     CS_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldq >= H * HD && ldkv >= 2 * H * HD && ldo >= H * HD,
                  "cs_attn_query_fwd: row strides must be multiples of 8 and cover the heads (ldq=%d ldkv=%d ldo=%d)", ldq, ldkv, ldo);
     CS_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)kv % 16) == 0, "cs_attn_query_fwd: q/kv must be 16-byte aligned");
-    return attn_cls_launch(q, kv, nullptr, nullptr, out, B * Q, Ntok, H, ldq, ldkv, ldo, scale, Q, allow, stream);
+    return attn_cls_launch(q, kv, nullptr, nullptr, out, B * Q, Ntok, H, ldq, ldkv, ldo, scale, Q, allow, lse, stream);
 }

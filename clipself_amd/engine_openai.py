@@ -10,7 +10,7 @@ does each stage (paths under /root/reference/src/open_clip/):
   MLP             transformer.py:209-213,31-34   GELU (erf) or QuickGELU
   image head      transformer.py:486-494     ln_post(x[:,0]) @ proj
   dense head      transformer.py:576-587     normalize(ln_post(x[:,1:]) @ proj)
-  mask attention  transformer.py:660-671,736-834   extract_type='v1' / encode_masks(mask_attn=True): extra query tokens (mask_attn_pool, inference)
+  mask attention  transformer.py:660-671,736-834   extract_type='v1' / encode_masks(mask_attn=True): extra query tokens (mask_attn_pool / backward_mask_attn)
   lock            transformer.py:391-422     groups = [stem, positional_embedding, blocks..., last block]; the last n train
                                              (n > L: positional_embedding, then conv1 / class_embedding / ln_pre: _stem_bwd)
 
@@ -62,6 +62,7 @@ class ClipVitEngine(TowerEngine):
         self.fold_cls_block = True                              # ln_1 of the CLS-only block folded into its K|V GEMM (A/B switch)
         # lock() with more groups than blocks (transformer.py:391-422): 1 = positional_embedding trains, 2 = conv1 / class_embedding / ln_pre too
         self.stem_level = 0
+        self._ctx_mask = None                                   # mask_attn_pool(need_grad=True) -> backward_mask_attn (its own slot: a v2 context survives)
 
     def _layout(self):
         return clip_vit_layout(self.cfg, self.prefix)
@@ -315,14 +316,17 @@ class ClipVitEngine(TowerEngine):
         return xc
 
     # ------------------------------------------------------------------------------------------ mask-attention pooling (inference)
-    def mask_attn_pool(self, images, masks, chunk: int = 64):
+    def mask_attn_pool(self, images, masks, chunk: int = 64, need_grad: bool = False):
         """VisionTransformer.mask_attn_pool / _mask_attn_pool (transformer.py:736-834), the pooling behind extract_type='v1' (:660-671) and
         encode_masks(mask_attn=True).  masks: list over images of bool [n_i, g, g] on the token grid.  Every mask is an extra token -- a copy
         of the image's CLS embedding after ln_pre -- that runs through ALL blocks; the reference's attention mask hides the extra tokens from
         everybody and lets token q see the CLS token plus the image tokens inside its mask, so the image tokens are exactly forward()'s and
         an extra token is a query-only passenger.  Per block: the image tokens' usual q|k|v GEMM, whose k|v columns also serve the Q extra
         queries of the image (cs_attn_query_fwd), then out_proj / MLP on the [B*Q, C] passenger stream with the same GEMM epilogues as the
-        blocks.  Images with fewer masks are padded with see-everything tokens whose rows are dropped (:793-795,823-824).  -> fp32 [sum n_i, E]"""
+        blocks.  Images with fewer masks are padded with see-everything tokens whose rows are dropped (:793-795,823-824).  -> fp32 [sum n_i, E]
+        With need_grad the whole batch runs in one pass that keeps what backward_mask_attn() needs (_mask_attn_pool_train)."""
+        if need_grad:
+            return self._mask_attn_pool_train(images, masks)
         ops, cfg, P = self.ops, self.cfg, self.prefix
         C, Hd, H, eps, E = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps, cfg.embed_dim
         counts = [int(m.shape[0]) for m in masks]
@@ -341,7 +345,7 @@ class ClipVitEngine(TowerEngine):
             allow = torch.ones((B, Q, N), dtype=torch.uint8, device=self.device)
             for b, m in enumerate(masks[k0:k0 + B]):
                 assert tuple(m.shape[1:]) == (g, g), f"masks live on the {g}x{g} token grid, got {tuple(m.shape[1:])}"
-                allow[b, :m.shape[0], 1:] = m.reshape(m.shape[0], -1).to(device=self.device, dtype=torch.uint8)
+                allow[b, :m.shape[0], 1:] = m.flatten(1).to(device=self.device, dtype=torch.uint8)
             allow = allow.view(B * Q, N)
             xf = x.view(B * N, C)
             xm = x[:, :1, :].expand(B, Q, C).reshape(B * Q, C).contiguous()          # fp32 passenger stream
@@ -382,15 +386,176 @@ class ClipVitEngine(TowerEngine):
             outs += [pooled[b, :n] for b, n in enumerate(counts[k0:k0 + B])]
         return torch.cat(outs)
 
+    # ------------------------------------------------------------------------------------------ mask-attention pooling (training)
+    def _allow_table(self, masks, B, Q, N, g):
+        allow = torch.ones((B, Q, N), dtype=torch.uint8, device=self.device)
+        for b, m in enumerate(masks):
+            assert tuple(m.shape[1:]) == (g, g), f"masks live on the {g}x{g} token grid, got {tuple(m.shape[1:])}"
+            allow[b, :m.shape[0], 1:] = m.flatten(1).to(device=self.device, dtype=torch.uint8)
+        return allow.view(B * Q, N)
+
+    def _mask_attn_pool_train(self, images, masks):
+        """mask_attn_pool() that keeps the activations of the trainable blocks (and of a trainable stem) for backward_mask_attn().  One row
+        stream [B*N + B*Q, C] per block -- the image tokens, then the passengers -- so LayerNorm, the GEMMs and the activation stay single
+        launches; only attention tells the two row sets apart (cs_attn_fwd on the image rows, cs_attn_query_fwd with its log-sum-exp on the
+        passengers, whose queries are the q columns of their rows of the q|k|v matrix).  The image tokens' output of the last block is
+        consumed by nobody: after its q|k|v GEMM that block runs on the passenger rows alone."""
+        ops, cfg, P = self.ops, self.cfg, self.prefix
+        C, Hd, H, eps, E = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps, cfg.embed_dim
+        counts = [int(m.shape[0]) for m in masks]
+        assert len(masks) == images.shape[0], "one mask list per image"
+        Q = max(counts) if counts else 0
+        if Q == 0:
+            self._ctx_mask = dict(empty=True)
+            return torch.zeros((0, E), dtype=F32, device=self.device)
+        B = images.shape[0]
+        stem_keep = {} if self._pos_trains() else None
+        x, g = self._stem(images, stem_keep)
+        N = g * g + 1
+        BN, MQ = B * N, B * Q
+        M = BN + MQ
+        cos, sin = self.rope_tables(g)
+        allow = self._allow_table(masks, B, Q, N, g)
+        scale = cfg.head_width ** -0.5
+        xs = ops.empty((M, C), F32)
+        xs[:BN] = x.view(BN, C)
+        xs[BN:] = x[:, :1, :].expand(B, Q, C).reshape(MQ, C)
+        saves = {}
+        for i in range(cfg.layers):
+            b_ = f"{P}{self.BLOCK_TAG}{i}."
+            last = i == cfg.layers - 1
+            keep = i >= self.first_trainable
+            R0 = BN if last else 0                                  # first row that continues past the attention
+            R = M - R0
+            st = (lambda n: (ops.empty((n,), F32), ops.empty((n,), F32))) if keep else (lambda n: (None, None))
+            ln1 = ops.empty((M, C), BF16)
+            m1, r1 = st(M)
+            ops.layernorm_fwd(xs, self.p[b_ + "ln_1.weight"], self.p[b_ + "ln_1.bias"], ln1, m1, r1, eps)
+            qkv = ops.empty((M, 3 * C), BF16)
+            ops.gemm_nt(ln1, self.w[b_ + "attn.in_proj_weight"], qkv, bias=self.p[b_ + "attn.in_proj_bias"], epi=EPI_BF16)
+            att = ops.empty((R, C), BF16)
+            lse = None
+            if not last:
+                lse = ops.empty((B * H, N), F32) if keep else None
+                ops.attn_fwd(qkv[:BN], cos, sin, att[:BN], lse, B, N, H, scale)
+            lse_m = ops.empty((B * H, Q), F32) if keep else None
+            ops.attn_query_fwd(qkv[BN:, :C], qkv[:BN, C:], allow, att[BN - R0:], B, Q, N, H, scale, **(dict(lse=lse_m) if keep else {}))
+            xin = xs[R0:]
+            x1 = ops.empty((R, C), F32) if keep else xin
+            ops.gemm_nt(att, self.w[b_ + "attn.out_proj.weight"], x1, bias=self.p[b_ + "attn.out_proj.bias"], extra=xin, epi=EPI_RESID_F32)
+            ln2 = ops.empty((R, C), BF16)
+            m2, r2 = st(R)
+            ops.layernorm_fwd(x1, self.p[b_ + "ln_2.weight"], self.p[b_ + "ln_2.bias"], ln2, m2, r2, eps)
+            hid = ops.empty((R, Hd), BF16)
+            fc = None
+            if keep:
+                fc = ops.empty((R, Hd), BF16)
+                ops.gemm_nt(ln2, self.w[b_ + "mlp.c_fc.weight"], fc, bias=self.p[b_ + "mlp.c_fc.bias"], epi=EPI_BF16)
+                ops.gelu_fwd(fc, hid, cfg.quick_gelu)
+            else:
+                ops.gemm_nt(ln2, self.w[b_ + "mlp.c_fc.weight"], hid, bias=self.p[b_ + "mlp.c_fc.bias"],
+                            epi=EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16)
+            x2 = ops.empty((R, C), F32) if keep else x1
+            ops.gemm_nt(hid, self.w[b_ + "mlp.c_proj.weight"], x2, bias=self.p[b_ + "mlp.c_proj.bias"], extra=x1, epi=EPI_RESID_F32)
+            if keep:
+                saves[i] = dict(x0=xs, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, lse_m=lse_m, att=att, with_attn=True, x1=x1, ln2=ln2,
+                                st2=(m2, r2), fc=fc, hid=hid, R0=R0)
+            xs = x2
+        xm = xs                                                      # [B*Q, C]: what the last block left
+        lnp = ops.empty((MQ, C), BF16)
+        mean, rstd = ops.empty((MQ,), F32), ops.empty((MQ,), F32)
+        ops.layernorm_fwd(xm, self.p[P + "ln_post.weight"], self.p[P + "ln_post.bias"], lnp, mean, rstd, eps)
+        pooled = ops.empty((MQ, E), F32)
+        self._head(lnp, pooled)
+        valid = torch.tensor([b * Q + r for b, n in enumerate(counts) for r in range(n)], dtype=torch.long, device=self.device)
+        self._ctx_mask = dict(B=B, N=N, Q=Q, g=g, saves=saves, xL=xm, stf=(mean, rstd), lnf=lnp if self.train_all else None, cos=cos, sin=sin,
+                              stem=stem_keep, allow=allow, valid=valid)
+        return pooled.index_select(0, valid)
+
+    def backward_mask_attn(self, d_pooled):
+        """d_pooled: fp32 [sum n_i, E], the gradient w.r.t. what mask_attn_pool(need_grad=True) returned.  The twin of backward_dense on the
+        [image tokens ; passengers] row stream: ln_post / proj from the passenger rows (train_all), per block the row-wise backward on both
+        row sets and cs_attn_bwd with the passengers as its `extra` rows (the last block: passengers only, no image rows), then the
+        passengers' gradient at the input of block 0 joins their image's CLS row -- they started as copies of it -- ahead of the stem.
+        Padding passengers carry a zero upstream gradient and contribute exact zeros.  Hooks fire in backward_dense's order."""
+        ops, cfg, P = self.ops, self.cfg, self.prefix
+        c = self._ctx_mask
+        if c is None:
+            raise RuntimeError("backward_mask_attn() without a preceding mask_attn_pool(need_grad=True)")
+        self._ctx_mask = None
+        if c.get("empty"):
+            return
+        B, N, Q, C, E, H = c["B"], c["N"], c["Q"], cfg.width, cfg.embed_dim, cfg.heads
+        BN, MQ = B * N, B * Q
+        M = BN + MQ
+        d_full = ops.zeros((MQ, E), F32)
+        d_full.index_copy_(0, c["valid"], d_pooled.to(F32))
+        d_feats = ops.empty((MQ, E), BF16)
+        ops.cast_f32_bf16(d_full, d_feats)
+        d_lnf = ops.empty((MQ, C), BF16)
+        self._head_dgrad(d_feats, d_lnf)
+        g = ops.zeros((M, C), F32)                    # image rows: nobody consumes the last block's image tokens
+        gb = ops.zeros((M, C), BF16)
+        ln_width, colsum_width = self._bwd_widths()
+        ws_bytes = max(ops.layernorm_bwd_workspace(M, ln_width), ops.attn_bwd_workspace(B, N, H, Q))
+        ws = (ops.empty((ws_bytes,), torch.uint8), ops.empty((max(ops.colsum_workspace(M, colsum_width), 4),), torch.uint8))
+        L, first, fn = cfg.layers, self.first_trainable, P + self.FINAL_NORM
+        resid_bias = lambda i: self.g[f"{P}{self.BLOCK_TAG}{i}.{self.RESID_BIAS}"] if i >= first else None
+        gm, gbm = g[BN:], gb[BN:]
+        if self.train_all:
+            self._head_wgrad(d_feats, c["lnf"], ws)
+            ops.layernorm_bwd(d_lnf, c["xL"], self.p[fn + ".weight"], *c["stf"], gm, DX_F32_ASSIGN,
+                              self.g[fn + ".weight"], self.g[fn + ".bias"], True, ws[0], dx_copy=gbm, copy_colsum=resid_bias(L - 1))
+            if self.grad_ready_hook is not None:
+                self.grad_ready_hook("head")
+        else:
+            ops.layernorm_bwd(d_lnf, c["xL"], self.p[fn + ".weight"], *c["stf"], gm, DX_F32_ASSIGN, None, None, True, ws[0],
+                              dx_copy=gbm if first < L else None, copy_colsum=resid_bias(L - 1))
+        for i in range(L - 1, first - 1, -1):
+            s = c["saves"].pop(i)
+            R0 = s["R0"]
+            d_att = self._block_bwd_mlp(i, s, g[R0:], gb[R0:], ws)
+            d_qkv = ops.empty((M, 3 * C), BF16)
+            d_qkv[BN:, C:] = 0                                    # passenger rows: dq | 0 | 0
+            qkv, att = s["qkv"], s["att"]
+            extra = dict(q=qkv[BN:, :C], o=att[BN - R0:], dout=d_att[BN - R0:], lse=s["lse_m"], allow=c["allow"], dq=d_qkv[BN:, :C], Q=Q)
+            if R0 == 0:
+                ops.attn_bwd(qkv[:BN], att[:BN], d_att[:BN], s["lse"], c["cos"], c["sin"], d_qkv[:BN], ws[0], B, N, H, cfg.head_width ** -0.5,
+                             extra=extra)
+            else:
+                ops.attn_bwd(qkv[:BN], None, None, None, c["cos"], c["sin"], d_qkv[:BN], ws[0], B, N, H, cfg.head_width ** -0.5, extra=extra)
+            self._block_bwd_ln1(i, s, d_qkv, 0, g, gb, ws, next_bias=resid_bias(i - 1) if i > 0 else None)
+            if self.grad_ready_hook is not None:
+                self.grad_ready_hook(i)
+        if c["stem"] is not None:
+            g3 = g[:BN].view(B, N, C)
+            g3[:, 0, :] += g[BN:].view(B, Q, C).sum(dim=1)       # every passenger started as a copy of its image's CLS row
+            self._stem_bwd(g[:BN], c["stem"], B, N, c["g"], ws[0])
+            if self.grad_ready_hook is not None:
+                self.grad_ready_hook("stem")
+
     # ------------------------------------------------------------------------------------------ backward
     def _block_bwd(self, i, s, g, gb, B, N, cos, sin, ws, next_bias=None, gq=None):
         """g: fp32 [M,C] gradient w.r.t. the block output; updated in place to the gradient w.r.t. its input.  gb: its bf16 copy, already summed
         into this block's c_proj bias gradient by the LayerNorm backward that produced it; on return gb is the copy of the new g and its column
         sums have gone to `next_bias` (block i-1's c_proj bias gradient, or None).  gq: always None here (no fp8 dgrad in this family)."""
         ops, cfg = self.ops, self.cfg
-        C, Hd, H = cfg.width, cfg.hidden, cfg.heads
+        C, H = cfg.width, cfg.heads
+        d_att = self._block_bwd_mlp(i, s, g, gb, ws)
+        if s["with_attn"]:
+            d_qkv = ops.empty((B * N, 3 * C), BF16)
+            ops.attn_bwd(s["qkv"], s["att"], d_att, s["lse"], cos, sin, d_qkv, ws[0], B, N, H, cfg.head_width ** -0.5)
+            self._block_bwd_ln1(i, s, d_qkv, 0, g, gb, ws, next_bias)
+        else:
+            self._block_bwd_ln1(i, s, d_att, 2 * C, g, gb, ws, next_bias)         # q/k rows keep their zero gradient
+
+    def _block_bwd_mlp(self, i, s, g, gb, ws):
+        """Row-wise half of a block's backward behind the attention: the MLP branch, ln_2 (g updated in place to the gradient w.r.t. x1, gb its
+        bf16 copy, whose column sums go to out_proj's bias) and out_proj.  -> d_att, bf16 [rows, C]."""
+        ops, cfg = self.ops, self.cfg
+        C, Hd = cfg.width, cfg.hidden
         b = f"{self.prefix}{self.BLOCK_TAG}{i}."
-        M = B * N
+        M = g.shape[0]
         G = self.g
         # ---- MLP: x2 = x1 + c_proj(act(c_fc(ln_2 x1))) --------------------------------------------
         self._wgrad(gb, s["hid"], G[b + "mlp.c_proj.weight"])
@@ -408,18 +573,20 @@ class ClipVitEngine(TowerEngine):
         self._wgrad(gb, s["att"], G[b + "attn.out_proj.weight"])
         d_att = ops.empty((M, C), BF16)
         ops.gemm_nt(gb, self.wt[(i, "proj")][:, :C], d_att, epi=EPI_BF16)
-        d_ln1 = ops.empty((M, C), BF16)
-        Gw, Gb = G[b + "attn.in_proj_weight"], G[b + "attn.in_proj_bias"]
-        if s["with_attn"]:
-            d_qkv = ops.empty((M, 3 * C), BF16)
-            ops.attn_bwd(s["qkv"], s["att"], d_att, s["lse"], cos, sin, d_qkv, ws[0], B, N, H, cfg.head_width ** -0.5)
-            ops.colsum_bf16(d_qkv, Gb, ws[1])                                                # q, k and v all carry a bias here
-            self._wgrad(d_qkv, s["ln1"], Gw)
-            ops.gemm_nt(d_qkv, self.wt[(i, "qkv")][:, :3 * C], d_ln1, epi=EPI_BF16)
-        else:
-            ops.colsum_bf16(d_att, Gb[2 * C:], ws[1])                                        # q/k rows keep their zero gradient
-            self._wgrad(d_att, s["ln1"], Gw[2 * C:])
-            ops.gemm_nt(d_att, self.wt[(i, "qkv")][:, 2 * C:3 * C], d_ln1, epi=EPI_BF16)
+        return d_att
+
+    def _block_bwd_ln1(self, i, s, d, col0, g, gb, ws, next_bias=None):
+        """... and the half in front of it: d = gradient w.r.t. columns [col0, 3C) of the q|k|v GEMM's output (col0 = 2C: the value third alone,
+        the block without attention) -> in_proj's gradients, then ln_1 (g += the gradient w.r.t. the block input; gb / next_bias as in
+        _block_bwd)."""
+        ops, cfg = self.ops, self.cfg
+        C = cfg.width
+        b = f"{self.prefix}{self.BLOCK_TAG}{i}."
+        G = self.g
+        d_ln1 = ops.empty((d.shape[0], C), BF16)
+        ops.colsum_bf16(d, G[b + "attn.in_proj_bias"][col0:], ws[1])                         # q, k and v all carry a bias here
+        self._wgrad(d, s["ln1"], G[b + "attn.in_proj_weight"][col0:])
+        ops.gemm_nt(d, self.wt[(i, "qkv")][:, col0:3 * C], d_ln1, epi=EPI_BF16)
         ops.layernorm_bwd(d_ln1, s["x0"], self.p[b + "ln_1.weight"], *s["st1"], g, DX_F32_ACCUM,
                           G[b + "ln_1.weight"], G[b + "ln_1.bias"], True, ws[0], dx_copy=gb if next_bias is not None else None,
                           copy_colsum=next_bias)

@@ -49,9 +49,9 @@ SIGNATURES = {
     "cs_l2norm_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "cs_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "cs_attn_cls_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "cs_attn_query_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "cs_attn_bwd_workspace": (_sz, [_i, _i, _i]),
-    "cs_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "cs_attn_query_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "cs_attn_bwd_workspace": (_sz, [_i, _i, _i, _i]),
+    "cs_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "cs_swiglu_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _vp]),
     "cs_swiglu_bwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _vp]),
     "cs_swiglu_bwd_colsum": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _i, _i, _vp]),
@@ -76,6 +76,11 @@ SIGNATURES = {
     "cs_stream_destroy": (_i, [_vp]),
     "cs_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp]),
 }
+
+
+class AttnExtra(ctypes.Structure):
+    """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
+    _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
 
 
 def library_path() -> Path:
@@ -131,6 +136,7 @@ class HipOps:
     become the `ld*` arguments.  Outputs are written in place into caller-allocated tensors."""
 
     name = "hip"
+    ATTN_EXTRA_QUERIES = True           # attn_query_fwd(lse=) / attn_bwd(extra=): mask-attention pooling is differentiable on this backend
 
     def __init__(self):
         self.lib = load_library()
@@ -463,21 +469,50 @@ class HipOps:
         self._ok(self.lib.cs_attn_cls_fwd(_p(q), _p(kv), _p(cos), _p(sin), _p(out), B, Ntok, H, q.stride(0), kv.stride(0),
                                           out.stride(0), scale, self._stream()), "cs_attn_cls_fwd")
 
-    def attn_query_fwd(self, q, kv, allow, out, B, Q, Ntok, H, scale):
-        """Q extra query rows per image against the image's keys / values; allow [B*Q, Ntok] uint8 (1 = may attend).  Inference only."""
-        self._chk(q, kv, allow, out)
+    def attn_query_fwd(self, q, kv, allow, out, B, Q, Ntok, H, scale, lse=None):
+        """Q extra query rows per image against the image's keys / values; allow [B*Q, Ntok] uint8 (1 = may attend).  lse [B*H, Q] f32
+        (optional): the rows' log-sum-exp over their allowed keys, what attn_bwd(extra=) needs."""
+        self._chk(q, kv, allow, out, lse)
         assert allow.dtype == torch.uint8 and allow.is_contiguous() and tuple(allow.shape) == (B * Q, Ntok)
-        self._ok(self.lib.cs_attn_query_fwd(_p(q), _p(kv), _p(allow), _p(out), B, Q, Ntok, H, q.stride(0), kv.stride(0), out.stride(0),
+        assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * H * Q)
+        self._ok(self.lib.cs_attn_query_fwd(_p(q), _p(kv), _p(allow), _p(out), _p(lse), B, Q, Ntok, H, q.stride(0), kv.stride(0), out.stride(0),
                                             scale, self._stream()), "cs_attn_query_fwd")
 
-    def attn_bwd_workspace(self, B, Ntok, H) -> int:
-        return int(self.lib.cs_attn_bwd_workspace(B, Ntok, H))
+    def attn_bwd_workspace(self, B, Ntok, H, Q=0) -> int:
+        return int(self.lib.cs_attn_bwd_workspace(B, Ntok, H, Q))
 
-    def attn_bwd(self, qkv, o, dout, lse, cos, sin, dqkv, workspace, B, Ntok, H, scale):
+    def _check_identity_tables(self, cos, sin):
+        """Extra query rows exist in the family without rotary embedding only: cos = 1, sin = 0 (checked once per table tensor)."""
+        key = ("ident", cos.data_ptr(), sin.data_ptr(), tuple(cos.shape))
+        seen = self.__dict__.setdefault("_rope_ok", set())
+        if key in seen:
+            return
+        if not (bool((cos == 1).all()) and bool((sin == 0).all())):
+            raise ValueError("attn_bwd(extra=...): extra query rows are not rotated, so the rotary tables must be the identity (cos 1, sin 0)")
+        seen.add(key)
+
+    def attn_bwd(self, qkv, o, dout, lse, cos, sin, dqkv, workspace, B, Ntok, H, scale, extra=None):
+        """extra: dict(q, o, dout, lse, allow, dq, Q) -- the extra query rows of the launch (cs_attn_extra); o / dout / lse may then be None."""
         self._chk(qkv, o, dout, lse, cos, sin, dqkv, workspace)
-        assert o.stride(0) == dout.stride(0) and qkv.stride(0) == dqkv.stride(0)
+        assert qkv.stride(0) == dqkv.stride(0)
+        if extra is None:
+            assert o.stride(0) == dout.stride(0)
+            self._ok(self.lib.cs_attn_bwd(_p(qkv), _p(o), _p(dout), _p(lse), _p(cos), _p(sin), _p(dqkv), _p(workspace), B, Ntok, H,
+                                          qkv.stride(0), o.stride(0), scale, None, self._stream()), "cs_attn_bwd")
+            return
+        q, eo, edo, elz, allow, dq, Q = (extra[k] for k in ("q", "o", "dout", "lse", "allow", "dq", "Q"))
+        self._chk(q, eo, edo, elz, allow, dq)
+        self._check_identity_tables(cos, sin)
+        assert (o is None) == (dout is None) == (lse is None), "image rows: o, dout and lse together or not at all"
+        assert o is None or o.stride(0) == dout.stride(0)
+        assert eo.stride(0) == edo.stride(0) and all(t.stride(1) == 1 for t in (q, eo, edo, dq))
+        assert q.shape[0] == B * Q and eo.shape[0] == B * Q and dq.shape[0] == B * Q
+        assert allow.dtype == torch.uint8 and allow.is_contiguous() and tuple(allow.shape) == (B * Q, Ntok)
+        assert elz.dtype == torch.float32 and elz.is_contiguous() and elz.numel() == B * H * Q
+        assert workspace.numel() * workspace.element_size() >= self.attn_bwd_workspace(B, Ntok, H, Q)
+        ex = AttnExtra(_p(q), _p(eo), _p(edo), _p(elz), _p(allow), _p(dq), Q, q.stride(0), eo.stride(0), dq.stride(0))
         self._ok(self.lib.cs_attn_bwd(_p(qkv), _p(o), _p(dout), _p(lse), _p(cos), _p(sin), _p(dqkv), _p(workspace), B, Ntok, H,
-                                      qkv.stride(0), o.stride(0), scale, self._stream()), "cs_attn_bwd")
+                                      qkv.stride(0), o.stride(0) if o is not None else H * 64, scale, ctypes.byref(ex), self._stream()), "cs_attn_bwd")
 
     def swiglu_fwd(self, x12, h):
         self._chk(x12, h)

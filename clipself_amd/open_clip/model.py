@@ -12,8 +12,8 @@ src/open_clip/eva_clip/eva_vit_model.py:396-711 `EVAVisionTransformer`):
 
 Every `visual.*` parameter is an nn.Parameter *view* into the engine's flat fp32 master buffer, and its `.grad`
 is a view into the flat grad buffer, so torch-side tools (state_dict, optimizers, checkpoints) see ordinary
-parameters while the kernels see four contiguous arrays.  Gradients enter torch autograd through two
-autograd.Functions (dense map, RoI pooling); everything between them is the engine's explicit schedule.
+parameters while the kernels see four contiguous arrays.  Gradients enter torch autograd through three
+autograd.Functions (dense map, RoI pooling, mask-attention pooling); everything between them is the engine's explicit schedule.
 """
 from __future__ import annotations
 
@@ -49,6 +49,24 @@ class _DenseFn(torch.autograd.Function):
         tower.engine.backward_dense(d_dense.contiguous())
         tower._attach_grads()
         return None, None, None
+
+
+class _MaskAttnFn(torch.autograd.Function):
+    """Mask-attention pooling (extract_type='v1' / encode_masks(mask_attn=True)) of a trainable tower: engine.mask_attn_pool(need_grad=True)
+    and engine.backward_mask_attn, gradients attached like _DenseFn's."""
+
+    @staticmethod
+    def forward(ctx, anchor, tower, images, masks):
+        ctx.tower = tower
+        return tower.engine.mask_attn_pool(images, masks, need_grad=True)
+
+    @staticmethod
+    def backward(ctx, d_pooled):
+        tower = ctx.tower
+        tower._prepare_grads()
+        tower.engine.backward_mask_attn(d_pooled.contiguous())
+        tower._attach_grads()
+        return None, None, None, None
 
 
 class _RoiFn(torch.autograd.Function):
@@ -343,21 +361,35 @@ class ClipVisionTower(EVAVisionTower):
 
     def extract_roi_features(self, x, normed_boxes, extract_type="v2", **kwargs):
         """The reference dispatches `extract_type` for this family (open_clip/transformer.py:515-521): 'v2' = the dense map + RoIAlign
-        (differentiable), 'v1' = every box rasterised on the token grid and pooled by an extra query token (:660-671; inference)."""
+        (differentiable), 'v1' = every box rasterised on the token grid and pooled by an extra query token (:660-671; differentiable too:
+        mask_attn_pool).  normed_boxes: a list of [k_i, 4] tensors per image, or the [K, 5] rois tensor with the image index in column 0."""
         if extract_type == "v1":
             g = x.shape[-1] // self.cfg.patch_size
+            if isinstance(normed_boxes, torch.Tensor) and normed_boxes.dim() == 2 and normed_boxes.shape[1] == 5:
+                # the [K, 5] rois the methods pass (image index first, rows grouped by image): one box list per image, possibly empty
+                idx = normed_boxes[:, 0].detach().to("cpu").long()
+                boxes = normed_boxes[:, 1:].detach().to("cpu")
+                assert bool((idx[1:] >= idx[:-1]).all()), "rois must be grouped by image, in image order"
+                normed_boxes = [boxes[idx == b] for b in range(x.shape[0])]
             return self.mask_attn_pool(x, [boxes_to_grid_masks(b, g, g) for b in normed_boxes])
         if extract_type != "v2":
             raise NotImplementedError(f"extract_type={extract_type!r}: the reference builds 'v1' and 'v2' (transformer.py:515-521)")
         return super().extract_roi_features(x, normed_boxes)
 
     def mask_attn_pool(self, image, masks):
-        """VisionTransformer.mask_attn_pool (transformer.py:785-834): one extra query token per mask through every block.  Forward only: the
-        hand-written backward does not cover the extra tokens, so a call that would need their gradient raises instead of silently detaching."""
+        """VisionTransformer.mask_attn_pool (transformer.py:785-834): one extra query token per mask through every block.  A trainable tower
+        under autograd differentiates it (_MaskAttnFn) when its kernel backend can -- `ops.ATTN_EXTRA_QUERIES`: attn_query_fwd(lse=) and
+        attn_bwd(extra=) -- and raises otherwise instead of silently detaching."""
+        image, masks = image.to(self.engine.device), list(masks)
         if torch.is_grad_enabled() and self._trainable():
-            raise NotImplementedError("mask-attention pooling (extract_type='v1' / mask_attn=True) is built for inference: call it under "
-                                      "torch.no_grad() or on a frozen tower; the training step differentiates extract_type='v2' only")
-        return self.engine.mask_attn_pool(image.to(self.engine.device), list(masks))
+            ops = self.engine.ops
+            if not getattr(ops, "ATTN_EXTRA_QUERIES", False):
+                raise NotImplementedError(f"mask-attention pooling (extract_type='v1' / mask_attn=True) needs the backward of the extra query "
+                                          f"tokens, which the kernel backend {getattr(ops, 'name', type(ops).__name__)!r} does not provide "
+                                          f"(no ATTN_EXTRA_QUERIES): call it under torch.no_grad() or on a frozen tower, or train with "
+                                          f"extract_type='v2'")
+            return _MaskAttnFn.apply(self._anchor, self, image, masks)
+        return self.engine.mask_attn_pool(image, masks)
 
     def _register_tables(self):
         pass                                                # no rotary tables in this family

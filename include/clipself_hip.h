@@ -153,16 +153,41 @@ int cs_attn_cls_fwd(const void* q, const void* kv, const float* cos_t, const flo
  * (src/open_clip/transformer.py:736-834), reached through extract_type='v1' (:660-671) and CLIP.encode_masks(mask_attn=True)
  * (src/open_clip/model.py:245-247).  Q query rows per image attend the image's own keys / values of the same depth: key j of query row r
  * is allowed iff allow[r * Ntok + j] != 0 (the reference's bool attn_mask, inverted; key 0 = the CLS token).  q [B*Q, ldq] bf16;
- * kv [B*Ntok, ldkv] bf16 = k|v; out [B*Q, ldo] bf16.  No rotary embedding in this family.  Inference only (no backward).  A row that allows
- * no key at all (the reference always allows key 0) yields a zero output row, not NaN. */
-int cs_attn_query_fwd(const void* q, const void* kv, const unsigned char* allow, void* out, int B, int Q, int Ntok, int H,
+ * kv [B*Ntok, ldkv] bf16 = k|v; out [B*Q, ldo] bf16.  No rotary embedding in this family.  A row that allows
+ * no key at all (the reference always allows key 0) yields a zero output row, not NaN.
+ * lse (nullable) [B*H, Q] f32: the natural log-sum-exp of the scaled scores over the allowed keys of each (image, head, query), +inf for a
+ * query that allows no key (its probabilities are exactly 0 in the backward).  With lse == NULL the output is bit-identical to the call
+ * without it.  Differentiated by cs_attn_bwd's `extra` argument (the reference trains through this path: no no_grad on :659-671,736-834). */
+int cs_attn_query_fwd(const void* q, const void* kv, const unsigned char* allow, void* out, float* lse, int B, int Q, int Ntok, int H,
                       int ldq, int ldkv, int ldo, float scale, cs_stream_t stream);
 /* cs_attn_fwd that also emits stats_part [H][B*Ntok][2] f32 = per head (sum, sum of squares) of each output row's 64 values. */
 int cs_attn_fwd_stats(const void* qkv, const float* cos_t, const float* sin_t, void* out, float* lse, float* stats_part, int B, int Ntok,
                       int H, int ldqkv, int ldo, float scale, cs_stream_t stream);
-size_t cs_attn_bwd_workspace(int B, int Ntok, int H);
+/* The extra query rows ("passengers") of a cs_attn_bwd launch: the Q rows per image that cs_attn_query_fwd ran against the image's keys /
+ * values.  q [B*Q, ldq] bf16; o, dout [B*Q, ldo] bf16 (the forward's output and its gradient); lse [B*H, Q] f32 from the forward;
+ * allow [B*Q, Ntok] bytes; dq [B*Q, lddq] bf16 (output).  Per image, head, passenger r and key j, with the rounding points of the image rows:
+ *   p = allow ? exp(scale * q_r.k_j - lse_r) : 0,  D_r = sum dO_r * O_r,  dS = bf16(p * (dO_r.v_j - D_r) * scale),
+ *   dq_r = sum_j dS * k_j,  dk_j += sum_r dS * q_r,  dv_j += sum_r bf16(p) * dO_r. */
+typedef struct cs_attn_extra {
+    const void* q;
+    const void* o;
+    const void* dout;
+    const float* lse;
+    const unsigned char* allow;
+    void* dq;
+    int Q, ldq, ldo, lddq;
+} cs_attn_extra;
+/* Q: extra query rows per image of the launch (0 = none). */
+size_t cs_attn_bwd_workspace(int B, int Ntok, int H, int Q);
+/* o, dout [B*Ntok, ldo] bf16; lse from cs_attn_fwd; dqkv [B*Ntok, ldqkv] bf16 = d(q|k|v) w.r.t. the un-rotated q, k.
+ * extra (nullable): the k|v columns of dqkv then hold the image tokens' own gradient plus the passengers' sums (added once, in fp32, after
+ * the image rows' kernels; the q columns are not touched by them) and extra->dq receives the passengers' dq.  With extra, o / dout / lse may
+ * all be NULL -- a launch without image rows (the last block of the pooling, whose image-token outputs nobody consumes): dqkv =
+ * [0 | passenger dK | passenger dV].  Passengers exist in the family without rotary embedding only: the tables must be the identity then.
+ * No atomics: bit-reproducible.  extra == NULL: every output is bit-identical to the call without the argument. */
 int cs_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, const float* cos_t, const float* sin_t,
-                void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, cs_stream_t stream);
+                void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, const cs_attn_extra* extra,
+                cs_stream_t stream);
 
 /* --- SwiGLU elementwise: eva_vit_model.py:101  hidden = silu(x1) * x2   (x12 = [x1 | x2], each Hd wide) */
 int cs_swiglu_fwd(const void* x12, long ldx, void* h, long ldh, int M, int Hd, cs_stream_t stream);
