@@ -28,7 +28,7 @@ class TowerCfg:
     mlp_ratio: float = 2.6667
     pt_hw_seq_len: int = 16  # RoPE pre-training grid (rope.py:96-142)
     ln_eps: float = 1e-6     # eva_clip/model.py:123
-    # text tower census only (state-dict compat; never executed on the hot path)
+    # text tower: frozen, off the training step; encode_text runs it when its head dim is 64 (engine_text.py)
     text_width: int = 512
     text_heads: int = 8
     text_layers: int = 12
@@ -127,6 +127,19 @@ def tiny_openai14_cfg() -> TowerCfg:
     """ViT-L/14-shaped miniature of the OpenAI family: patch 14 (3*14*14 = 588 -> conv1 stored with K padded to 640), 3x3 grid."""
     return TowerCfg(name="ViT-tiny14-test", embed_dim=64, image_size=42, patch_size=14, width=128, layers=2, head_width=64, mlp_ratio=4.0,
                     ln_eps=1e-5, text_width=32, text_heads=2, text_layers=1, text_context=8, text_vocab=64, arch="openai")
+
+
+def tiny_text_cfg(arch: str = "openai", quick_gelu: bool = False, context: int = 16) -> TowerCfg:
+    """The tiny towers above with a text tower the kernels can run (theirs has head dim 16): text width 128 / 2 heads (head dim 64 like
+    every shipped text config: 512 / 8, 768 / 12), 2 layers, vocab 64 -- for the encode_text golden vectors."""
+    text = dict(text_width=128, text_heads=2, text_layers=2, text_context=context, text_vocab=64)
+    tag = ("-quickgelu" if quick_gelu else "") + (f"-ctx{context}" if context != 16 else "")
+    if arch == "openai":
+        return TowerCfg(name="ViT-tiny-text-test" + tag, embed_dim=64, image_size=32, patch_size=8, width=128, layers=2, head_width=64,
+                        mlp_ratio=4.0, ln_eps=1e-5, arch="openai", quick_gelu=quick_gelu, **text)
+    assert arch == "eva02" and not quick_gelu
+    return TowerCfg(name="EVA02-tiny-text-test" + tag, embed_dim=64, image_size=32, patch_size=8, width=128, layers=2, head_width=64,
+                    mlp_ratio=2.0, **text)
 
 
 def cfg_dict(cfg: TowerCfg) -> dict:

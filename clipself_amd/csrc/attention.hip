@@ -1338,6 +1338,156 @@ __global__ __launch_bounds__(256) void attn_pass_dq_kernel(PassArgs p, long tota
     *(uint4*)(p.dq + ((size_t)b * p.Q + r) * p.lddq + h * HD + c * 8) = out.u;
 }
 
+// ------------------------------------------------------------------------------------------------ causal self-attention (text tower)
+// cs_attn_query_fwd(allow == NULL): query row r of a sequence attends keys 0..r of the same sequence (the text transformer's additive
+// triu(-inf) mask: open_clip/model.py:269-281, eva_clip/transformer.py:714-737), sequences of L <= 128 tokens, no rotary tables.
+//   * a "unit" is one (sequence, head); it owns NT = ceil(L / 32) waves, one 32-query tile each, and its own LDS images (K in the k_off
+//     layout, V^T), staged once by the unit's NT * 64 threads.  A workgroup carries UPW units -- at L <= 32 (the common case once the text
+//     engine has trimmed a batch to its longest prompt) a unit is ONE wave, and a one-unit workgroup would leave the other waves idle.
+//   * wave t attends key tiles 0..t only (wave-uniform), the diagonal tile is masked per element (score -> -inf: p = 0 exactly).  All of a
+//     row's scores fit in registers (<= 4 tiles), so the softmax is a single pass: no running maximum, no rescale of the accumulators.
+//     Same rounding points as the forward kernels above: fp32 scores, exp2 of the scaled difference to the row maximum, P rounded to
+//     bf16 for the P.V MFMA, fp32 row sum of the unrounded exponentials, one rounding of o / l to bf16.
+//   * rows past the sequence end re-read its last row (queries: computed, not stored; keys: above every stored query's diagonal).
+//   * V^T rows hold VLD = 32 / 64 / 128 keys; their 8-key blocks are XOR-permuted by bits of the dim chosen per VLD so that the 16 lanes
+//     ds_read_b128 serves per cycle ({0-3,12-15,20-27}, {4-11,16-19,28-31} of a wave half) fall on 16 different 16-byte slots of the
+//     256-byte LDS row: VLD 128 -> d & 15, VLD 64 -> (d >> 1) & 7 (+ the row parity), VLD 32 -> (d >> 2) & 3 (+ d & 3).
+struct CausalArgs {
+    const __bf16* q;       // [B*L, ldq]
+    const __bf16* kv;      // [B*L, ldkv] = k | v
+    __bf16* out;           // [B*L, ldo]
+    int L, H, units;       // units = B * H
+    int ldq, ldkv, ldo;
+    int wide;              // out rows are 16-byte aligned: store_o's 16-byte stores (else 2-byte stores)
+    float scale;
+};
+
+template <int NT>
+struct CausalGeo {
+    static constexpr int VLD = NT == 1 ? 32 : (NT == 2 ? 64 : 128);       // keys per V^T row (NT = 3 leaves blocks 12..15 unused)
+    static constexpr int NB = VLD / 8, SH = NT == 1 ? 2 : (NT == 2 ? 1 : 0);
+    static constexpr int KBYTES = NT * 32 * 128, VBYTES = HD * VLD * 2;
+    static __device__ __forceinline__ int vt_off(int d, int kb) { return d * VLD + ((kb ^ ((d >> SH) & (NB - 1))) << 3); }
+};
+
+// key tiles 0 .. KT-1 against the 32-query tile KT-1 (the last key tile is the diagonal one); qc = the lane's query row, clamped
+template <int KT, int NT>
+__device__ __forceinline__ void causal_attend(const char* Kl, const __bf16* Vt, const bf16x8 (&qf)[4], int qc, float sl2, int lane, float& l,
+                                              f32x16 (&o)[2]) {
+    const int hf = lane >> 5, l31 = lane & 31;
+    const int k_base = (l31 >> 1) << 8, par8 = (l31 & 1) << 3, sw = l31 >> 1;      // k_off of row t * 32 + l31, as in attend_chunk
+    f32x16 s[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        s[t] = zero16();
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const bf16x8 kfrag = *(const bf16x8*)(Kl + t * (16 * 256) + k_base + (((par8 | (ks * 2 + hf)) ^ sw) << 4));
+            s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qf[ks], s[t], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+        if ((KT - 1) * 32 + mfma32_row(e, lane) > qc) s[KT - 1][e] = -INFINITY;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < KT; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[t][e]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));                  // key 0 is never masked: mx is finite
+    const float msc = mx * sl2;
+    float rs = 0.f;
+#pragma unroll
+    for (int t = 0; t < KT; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float pv = __builtin_amdgcn_exp2f(s[t][e] * sl2 - msc);
+            s[t][e] = pv;
+            rs += pv;
+        }
+    l = rs + __shfl_xor(rs, 32, 64);
+#pragma unroll
+    for (int t = 0; t < KT; ++t)
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2) {
+            const bf16x8 pb = pack8_swapped(s[t], c2);
+            const int kb = t * 4 + c2 * 2 + hf;              // key block (8 keys) this half supplies
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                const bf16x8 vfrag = *(const bf16x8*)(Vt + CausalGeo<NT>::vt_off(dt * 32 + l31, kb));
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfrag, pb, o[dt], 0, 0, 0);
+            }
+        }
+}
+
+template <int NT, int UPW>
+__global__ __launch_bounds__(NT * UPW * 64) void attn_causal_kernel(CausalArgs p) {
+    using G = CausalGeo<NT>;
+    constexpr int UT = NT * 64, HALF = NT * 32;              // threads of a unit; its V stagers (the other half stages K)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5, l31 = lane & 31;
+    const int slot = wave / NT, t = wave - slot * NT, ut = tid - slot * UT;        // unit slot, query tile, thread within the unit
+    const int unit = blockIdx.x * UPW + slot;
+    const int u = min(unit, p.units - 1);                    // a slot past the last unit stages that unit again and stores nothing
+    const int b = u / p.H, h = u - b * p.H;
+    const int last = p.L - 1;
+    const size_t rowbase = (size_t)b * p.L;
+    char* Kl = smem + slot * (G::KBYTES + G::VBYTES);
+    __bf16* Vt = (__bf16*)(Kl + G::KBYTES);
+    // every global load ahead of the first LDS store.  Threads [0, HALF): one (8-key block, 8-dim chunk) item of V, its 8 key rows;
+    // threads [HALF, UT): 8 of the NT * 256 (key row, chunk) items of K.  Branch-free: HALF is half a wave at NT = 1.
+    const bool vrole = ut < HALF;
+    const int vkb = ut >> 3, c8 = ut & 7;                    // (ut - HALF) & 7 == ut & 7
+    const int kr0 = (ut - HALF) >> 3;
+    const __bf16* src = p.kv + h * HD + c8 * 8 + (vrole ? p.H * HD : 0);
+    U128 ld[8], qraw[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int tok = min(vrole ? vkb * 8 + i : kr0 + i * (NT * 4), last);
+        ld[i].u = *(const uint4*)(src + (rowbase + tok) * p.ldkv);
+    }
+    const int q = t * 32 + l31, qc = min(q, last);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qraw[ks].u = *(const uint4*)(p.q + (rowbase + qc) * p.ldq + h * HD + ks * 16 + hf * 8);
+    if (vrole) {                                             // 8x8 in-register transpose -> V^T image
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            U128 w;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) w.e[i] = ld[i].e[j];
+            *(uint4*)(Vt + G::vt_off(c8 * 8 + j, vkb)) = w.u;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) *(uint4*)(Kl + k_off(kr0 + i * (NT * 4), c8)) = ld[i].u;
+    }
+    __syncthreads();
+    if (unit >= p.units) return;
+    bf16x8 qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = qraw[ks].h;
+    const float sl2 = p.scale * LOG2E;
+    float l = 1.f;
+    f32x16 o[2] = {zero16(), zero16()};
+    if (t == 0) causal_attend<1, NT>(Kl, Vt, qf, qc, sl2, lane, l, o);
+    if constexpr (NT > 1) if (t == 1) causal_attend<2, NT>(Kl, Vt, qf, qc, sl2, lane, l, o);
+    if constexpr (NT > 2) if (t == 2) causal_attend<3, NT>(Kl, Vt, qf, qc, sl2, lane, l, o);
+    if constexpr (NT > 3) if (t == 3) causal_attend<4, NT>(Kl, Vt, qf, qc, sl2, lane, l, o);
+    if (q > last) return;
+    if (p.wide) {
+        AttnArgs a{};
+        a.out = p.out; a.ldo = p.ldo;
+        store_o(a, rowbase, q, h, u, hf, 0.f, l, o);
+    } else {                                                 // the same values, element by element (register g4 * 4 + i = dim g4 * 8 + hf * 4 + i)
+        const float inv = 1.f / l;
+        __bf16* orow = p.out + (rowbase + q) * p.ldo + h * HD;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) orow[dt * 32 + (e >> 2) * 8 + hf * 4 + (e & 3)] = f2bf(o[dt][e] * inv);
+    }
+}
+
 }  // namespace
 
 // C ABI ------------------------------------------------------------------------------------------
@@ -1543,14 +1693,54 @@ extern "C" int cs_attn_cls_fwd(const void* q, const void* kv, const float* cos_t
     return attn_cls_launch(q, kv, cos_t, sin_t, out, B, Ntok, H, ldq, ldkv, ldo, scale, 1, nullptr, nullptr, stream);
 }
 
+template <int NT, int UPW>
+static void attn_causal_run(const CausalArgs& a, hipStream_t stream) {
+    constexpr size_t lds = (size_t)UPW * (CausalGeo<NT>::KBYTES + CausalGeo<NT>::VBYTES);
+    static_assert(lds <= 64 * 1024, "the causal kernel stays inside the default dynamic-LDS limit");
+    hipLaunchKernelGGL((attn_causal_kernel<NT, UPW>), dim3((unsigned)(((long)a.units + UPW - 1) / UPW)), dim3(NT * UPW * 64), lds, stream, a);
+}
+
+// cs_attn_query_fwd(allow == NULL).  Units per workgroup: 4 one-wave units at L <= 32, 2 units of 2 / 3 / 4 waves above.
+static int attn_causal_launch(const void* q, const void* kv, void* out, const float* lse, int B, int Q, int Ntok, int H, int ldq, int ldkv,
+                              int ldo, float scale, hipStream_t stream) {
+    CS_CHECK_ARG(lse == nullptr, "cs_attn_query_fwd: allow == NULL (causal self-attention) has no lse output");
+    CS_CHECK_ARG(B > 0 && H > 0 && Ntok >= 1 && Ntok <= 128, "cs_attn_query_fwd: causal form needs B > 0, H > 0 and 1 <= Ntok <= 128 (B=%d Ntok=%d H=%d)",
+                 B, Ntok, H);
+    CS_CHECK_ARG(Q == Ntok, "cs_attn_query_fwd: causal form is self-attention, Q must equal Ntok (Q=%d Ntok=%d)", Q, Ntok);
+    CS_CHECK_ARG((long)B * H <= 0x7fffffffL, "cs_attn_query_fwd: B * H = %ld (sequence, head) units do not fit a launch", (long)B * H);
+    CS_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldq >= H * HD && ldkv >= 2 * H * HD && ldo >= H * HD,
+                 "cs_attn_query_fwd: row strides must be multiples of 8 and cover the heads (ldq=%d ldkv=%d ldo=%d)", ldq, ldkv, ldo);
+    CS_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)kv % 16) == 0, "cs_attn_query_fwd: q/kv must be 16-byte aligned");
+    CausalArgs a{};
+    a.q = (const __bf16*)q; a.kv = (const __bf16*)kv; a.out = (__bf16*)out;
+    a.L = Ntok; a.H = H; a.units = B * H; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.scale = scale;
+    a.wide = ((uintptr_t)out % 16) == 0 && ldo % 8 == 0;
+    switch ((Ntok + 31) / 32) {
+        case 1: attn_causal_run<1, 4>(a, stream); break;
+        case 2: attn_causal_run<2, 2>(a, stream); break;
+        case 3: attn_causal_run<3, 2>(a, stream); break;
+        default: attn_causal_run<4, 2>(a, stream); break;
+    }
+    CS_LAUNCH_CHECK();
+    return 0;
+}
+
 // Extra query tokens of the OpenAI-CLIP family's mask-attention pooling (open_clip/transformer.py:736-834, reached through
 // extract_type='v1' :660-671 and encode_masks(mask_attn=True), model.py:245-247): Q query rows per image against the image's own keys /
 // values of the same depth, key j of query row r allowed iff allow[r * Ntok + j] != 0 (key 0 = the CLS token, always allowed there).
 // q [B*Q, ldq] bf16; kv [B*Ntok, ldkv] bf16 = k|v; out [B*Q, ldo] bf16.  No rotary embedding in this family.  lse (nullable) [B*H, Q] f32:
 // the natural log-sum-exp of the scaled scores over a row's allowed keys (+inf for a row that allows none), for cs_attn_bwd's `extra`.
+//
+// allow == NULL: CAUSAL SELF-ATTENTION of B sequences of Ntok tokens (the text tower: open_clip/model.py:269-281,
+// eva_clip/transformer.py:714-737) -- query row r of sequence b attends keys 0..r of sequence b.  Requires Q == Ntok, lse == NULL and
+// 1 <= Ntok <= 128 (anything else is an argument error, never a launch); q [B*Ntok, ldq], kv [B*Ntok, ldkv] = k|v, out [B*Ntok, ldo]
+// (in practice q and kv are strided views of one [B*Ntok, 3C] q|k|v matrix); same stride and alignment rules as the masked form.
+// Rounding points of the forward kernels: fp32 scores, exp2 of the scaled difference to the row maximum, P rounded to bf16 before P.V,
+// fp32 row sum of the unrounded exponentials, one rounding to bf16.  Bit-reproducible.
 extern "C" int cs_attn_query_fwd(const void* q, const void* kv, const unsigned char* allow, void* out, float* lse, int B, int Q, int Ntok, int H,
                                  int ldq, int ldkv, int ldo, float scale, hipStream_t stream) {
-    CS_CHECK_ARG(q && kv && allow && out, "cs_attn_query_fwd: null pointer");
+    CS_CHECK_ARG(q && kv && out, "cs_attn_query_fwd: null pointer");
+    if (allow == nullptr) return attn_causal_launch(q, kv, out, lse, B, Q, Ntok, H, ldq, ldkv, ldo, scale, stream);
     CS_CHECK_ARG(B > 0 && Q > 0 && Ntok > 1 && H > 0, "cs_attn_query_fwd: bad sizes B=%d Q=%d Ntok=%d H=%d", B, Q, Ntok, H);
     CS_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldq >= H * HD && ldkv >= 2 * H * HD && ldo >= H * HD,
                  "cs_attn_query_fwd: row strides must be multiples of 8 and cover the heads (ldq=%d ldkv=%d ldo=%d)", ldq, ldkv, ldo);

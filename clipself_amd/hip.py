@@ -137,6 +137,7 @@ class HipOps:
 
     name = "hip"
     ATTN_EXTRA_QUERIES = True           # attn_query_fwd(lse=) / attn_bwd(extra=): mask-attention pooling is differentiable on this backend
+    ATTN_CAUSAL = True                  # attn_query_fwd(allow=None): causal self-attention, what the text tower (encode_text) runs on
 
     def __init__(self):
         self.lib = load_library()
@@ -471,8 +472,15 @@ class HipOps:
 
     def attn_query_fwd(self, q, kv, allow, out, B, Q, Ntok, H, scale, lse=None):
         """Q extra query rows per image against the image's keys / values; allow [B*Q, Ntok] uint8 (1 = may attend).  lse [B*H, Q] f32
-        (optional): the rows' log-sum-exp over their allowed keys, what attn_bwd(extra=) needs."""
+        (optional): the rows' log-sum-exp over their allowed keys, what attn_bwd(extra=) needs.
+        allow=None: causal self-attention of B sequences of Ntok <= 128 tokens (the text tower; Q == Ntok, no lse)."""
         self._chk(q, kv, allow, out, lse)
+        if allow is None:
+            assert Q == Ntok and lse is None and Ntok <= 128, "attn_query_fwd(allow=None) is causal self-attention: Q == Ntok <= 128, no lse"
+            assert q.stride(1) == 1 and kv.stride(1) == 1 and out.stride(1) == 1 and q.shape[0] == B * Ntok == kv.shape[0] == out.shape[0]
+            self._ok(self.lib.cs_attn_query_fwd(_p(q), _p(kv), None, _p(out), None, B, Q, Ntok, H, q.stride(0), kv.stride(0), out.stride(0),
+                                                scale, self._stream()), "cs_attn_query_fwd")
+            return
         assert allow.dtype == torch.uint8 and allow.is_contiguous() and tuple(allow.shape) == (B * Q, Ntok)
         assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * H * Q)
         self._ok(self.lib.cs_attn_query_fwd(_p(q), _p(kv), _p(allow), _p(out), _p(lse), B, Q, Ntok, H, q.stride(0), kv.stride(0), out.stride(0),

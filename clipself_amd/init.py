@@ -106,6 +106,48 @@ def seeded_visual_state(cfg: TowerCfg, seed: int = 0, prefix: str = "visual.") -
     return sd
 
 
+def text_param_shapes(cfg: TowerCfg, prefix: str = None) -> "dict[str, tuple]":
+    """Shapes of every parameter of the text tower under the reference's state-dict names: `text.*` in the EVA family
+    (eva_clip/model.py:284, transformer.py:663-677), top level in the OpenAI-CLIP family (open_clip/model.py:205-211)."""
+    if prefix is None:
+        prefix = "" if getattr(cfg, "arch", "eva02") == "openai" else "text."
+    W, E = cfg.text_width, cfg.embed_dim
+    out = {prefix + "positional_embedding": (cfg.text_context, W), prefix + "text_projection": (W, E),
+           prefix + "token_embedding.weight": (cfg.text_vocab, W)}
+    for i in range(cfg.text_layers):
+        b = f"{prefix}transformer.resblocks.{i}."
+        out.update({b + "ln_1.weight": (W,), b + "ln_1.bias": (W,), b + "attn.in_proj_weight": (3 * W, W), b + "attn.in_proj_bias": (3 * W,),
+                    b + "attn.out_proj.weight": (W, W), b + "attn.out_proj.bias": (W,), b + "ln_2.weight": (W,), b + "ln_2.bias": (W,),
+                    b + "mlp.c_fc.weight": (4 * W, W), b + "mlp.c_fc.bias": (4 * W,), b + "mlp.c_proj.weight": (W, 4 * W),
+                    b + "mlp.c_proj.bias": (W,)})
+    out[prefix + "ln_final.weight"] = (W,)
+    out[prefix + "ln_final.bias"] = (W,)
+    return out
+
+
+def seeded_text_state(cfg: TowerCfg, seed: int = 0, prefix: str = None) -> "dict[str, torch.Tensor]":
+    """fp32 CPU tensors for every text-tower parameter, from the same name-keyed streams as seeded_visual_state.  Matrices carry the
+    standard deviations of the reference's init_parameters (transformer.py:686-700: in_proj W^-0.5, out_proj / c_proj W^-0.5 (2L)^-0.5,
+    c_fc (2W)^-0.5, text_projection W^-0.5, token embedding 0.02, positions 0.01) so that the attention scores are O(1) and the softmax is
+    far from uniform; biases and LayerNorm affine terms are non-trivial as in the vision recipe."""
+    W, L = cfg.text_width, cfg.text_layers
+    sd = {}
+    for name, shape in text_param_shapes(cfg, prefix).items():
+        g = _rng(name, seed)
+        if name.endswith(("ln_1.weight", "ln_2.weight", "ln_final.weight")):
+            t = 1.0 + 0.1 * g.standard_normal(shape)
+        elif len(shape) == 1:
+            t = 0.02 * g.standard_normal(shape)
+        else:
+            std = (W ** -0.5 if name.endswith(("in_proj_weight", "text_projection")) else
+                   W ** -0.5 * (2 * L) ** -0.5 if name.endswith(("out_proj.weight", "c_proj.weight")) else
+                   (2 * W) ** -0.5 if name.endswith("c_fc.weight") else
+                   0.01 if name.endswith("positional_embedding") else 0.02)
+            t = std * g.standard_normal(shape)
+        sd[name] = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
+    return sd
+
+
 def synthetic_batch(batch: int, boxes_per_image: int, image_size: int, crop_size: int,
                     seed: int = 1234, rank: int = 0, valid_prob: float = 1.0):
     """SURVEY.md §8 M2 synthetic step input with the reference batch contract

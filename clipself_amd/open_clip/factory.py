@@ -180,5 +180,5 @@ def create_model_and_transforms(model_name: str, pretrained: Optional[str] = Non
 
 def get_tokenizer(model_name):
     def _no_text(*a, **k):
-        raise NotImplementedError("tokenisation / the text tower are outside the CLIPSelf hot path")
+        raise NotImplementedError("tokenisation is not built (no BPE table is shipped): encode_text takes token ids [B, context]")
     return _no_text

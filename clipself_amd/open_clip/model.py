@@ -7,6 +7,7 @@ src/open_clip/eva_clip/eva_vit_model.py:396-711 `EVAVisionTransformer`):
   model.encode_dense(x, normalize=False, keep_shape=False)             -> [B, hw, E] | [B, E, h, w]
   model.encode_pseudo_boxes(x, list[Tensor[k_i,4]], normalize=False, extract_type='v2') -> [K, E]
   model.encode_masks(x, masks, normalize=True)                         -> [sum masks, E]
+  model.encode_text(ids, normalize=False)                              -> [B, E]   (frozen text tower, engine_text.py; token ids in)
   model.lock_image_tower(unlocked_groups, freeze_bn_stats), .set_grad_checkpointing(), .logit_scale,
   model.visual.image_size / image_mean / image_std, .train() / .eval(), .state_dict() with the reference's keys.
 
@@ -25,6 +26,7 @@ import torch.nn.functional as F
 from ..config import TowerCfg
 from ..engine import EvaEngine, F32
 from ..engine_openai import ClipVitEngine
+from ..engine_text import TextEngine, validate_ids
 
 OPENAI_DATASET_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_DATASET_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -241,12 +243,14 @@ def boxes_to_rois(normed_boxes, device):
 
 class FrozenTextTower(nn.Module):
     """The reference constructs, freezes and checkpoints a TextTransformer that the distillation step never runs
-    (eva_clip/model.py:284-288).  Only its state-dict keys/shapes matter; they are held here as
-    frozen parameters so checkpoints round-trip."""
+    (eva_clip/model.py:284-288): its tensors are held here as frozen parameters under the reference's state-dict keys, so
+    checkpoints round-trip.  forward(text) -- what encode_text of both model families calls -- runs them on engine_text.TextEngine, which
+    is built, with its bf16 weight shadows, on the first call: a model that never encodes text pays nothing."""
 
-    def __init__(self, cfg: TowerCfg, device, mask_in_state_dict: bool = True):
+    def __init__(self, cfg: TowerCfg, device, mask_in_state_dict: bool = True, ops=None):
         super().__init__()
         self.mask_in_state_dict = mask_in_state_dict
+        self.cfg, self._ops, self._device, self._engine = cfg, ops, device, None
         W, L, E = cfg.text_width, cfg.text_layers, cfg.embed_dim
         shapes = {"positional_embedding": (cfg.text_context, W), "text_projection": (W, E),
                   "token_embedding.weight": (cfg.text_vocab, W), "ln_final.weight": (W,), "ln_final.bias": (W,)}
@@ -278,16 +282,31 @@ class FrozenTextTower(nn.Module):
                     self._parameters[safe].copy_(state_dict[prefix + k])
                 else:
                     missing_keys.append(prefix + k)
+        self.invalidate()
 
-    def forward(self, text):
-        raise NotImplementedError("the text tower is not on the CLIPSelf hot path (never executed by the reference's training step)")
+    def invalidate(self):
+        """The parameters changed (every load does this itself; call it after writing through `param.data`): encode_text rebuilds its
+        bf16 weight shadows on the next call."""
+        if self._engine is not None:
+            self._engine.invalidate()
+
+    def forward(self, text, return_all_features: bool = False, trim: bool = True, chunk: int = 4096):
+        """TextTransformer.forward (eva_clip/transformer.py:722-737): ids [B, text_context] -> fp32 [B, E], detached, on the engine's device.
+        trim=False runs every sequence at the full context instead of the batch's longest prompt (same features; engine_text.py)."""
+        if return_all_features:
+            raise NotImplementedError("return_all_features: only the pooled end-of-text feature is built")
+        validate_ids(text, self.cfg)
+        if self._engine is None:
+            ops = self._ops if self._ops is not None else _default_ops()
+            self._engine = TextEngine(self.cfg, ops, {k: self._parameters[safe] for safe, k in self._names.items()}, self._device)
+        return self._engine.encode(text, trim=trim, chunk=chunk)
 
 
 class CustomCLIP(nn.Module):
     def __init__(self, cfg: TowerCfg, ops=None, trainable: bool = True, with_text: bool = True):
         super().__init__()
         self.visual = EVAVisionTower(cfg, ops=ops, trainable=trainable)
-        self.text = FrozenTextTower(cfg, self.visual.engine.device) if with_text else None
+        self.text = FrozenTextTower(cfg, self.visual.engine.device, ops=self.visual.engine.ops) if with_text else None
         self.embed_dim = cfg.embed_dim
         self.logit_scale = nn.Parameter(torch.ones([], device=self.visual.engine.device) * np.log(1 / 0.07))
 
@@ -318,8 +337,16 @@ class CustomCLIP(nn.Module):
         features = self.visual(image)
         return F.normalize(features, dim=-1) if normalize else features
 
-    def encode_text(self, text, normalize: bool = False):
-        raise NotImplementedError("text encoding is outside the CLIPSelf hot path")
+    def _text_tower(self):
+        return self.text
+
+    def encode_text(self, text, normalize: bool = False, trim: bool = True):
+        """eva_clip/model.py:317-319 (CustomCLIP) and open_clip/model.py:269-281 (CLIP): token ids [B, text_context] -> fp32 [B, E]."""
+        tower = self._text_tower()
+        if tower is None:
+            raise RuntimeError("this model was built with with_text=False: it holds no text tower to encode with")
+        features = tower(text, trim=trim)
+        return F.normalize(features, dim=-1) if normalize else features
 
     def encode_dense(self, image, normalize: bool = False, keep_shape=False):
         features = self.visual.encode_dense(image, keep_shape=keep_shape)
@@ -408,10 +435,13 @@ class CLIP(CustomCLIP):
         nn.Module.__init__(self)
         self.visual = ClipVisionTower(cfg, ops=ops, trainable=trainable)
         self.text = None
-        text = FrozenTextTower(cfg, self.visual.engine.device, mask_in_state_dict=False) if with_text else None
+        text = FrozenTextTower(cfg, self.visual.engine.device, mask_in_state_dict=False, ops=self.visual.engine.ops) if with_text else None
         object.__setattr__(self, "_text", text)             # not a registered child: its keys carry no prefix
         self.embed_dim, self.vocab_size = cfg.embed_dim, cfg.text_vocab
         self.logit_scale = nn.Parameter(torch.ones([], device=self.visual.engine.device) * np.log(1 / 0.07))
+
+    def _text_tower(self):
+        return self._text
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         super()._save_to_state_dict(destination, prefix, keep_vars)

@@ -157,7 +157,18 @@ int cs_attn_cls_fwd(const void* q, const void* kv, const float* cos_t, const flo
  * no key at all (the reference always allows key 0) yields a zero output row, not NaN.
  * lse (nullable) [B*H, Q] f32: the natural log-sum-exp of the scaled scores over the allowed keys of each (image, head, query), +inf for a
  * query that allows no key (its probabilities are exactly 0 in the backward).  With lse == NULL the output is bit-identical to the call
- * without it.  Differentiated by cs_attn_bwd's `extra` argument (the reference trains through this path: no no_grad on :659-671,736-834). */
+ * without it.  Differentiated by cs_attn_bwd's `extra` argument (the reference trains through this path: no no_grad on :659-671,736-834).
+ *
+ * allow == NULL selects CAUSAL SELF-ATTENTION, the text tower's attention (src/open_clip/model.py:269-281, eva_clip/transformer.py:714-737:
+ * the additive triu(-inf) mask): B sequences of Ntok tokens, query row r of sequence b attends keys 0..r of sequence b.
+ *   - requires Q == Ntok and lse == NULL (inference only: no log-sum-exp, no backward);
+ *   - 1 <= Ntok <= 128 (the `Ntok > 1` rule is the masked form's); Ntok > 128 is an argument error, never a launch;
+ *   - q [B*Ntok, ldq], kv [B*Ntok, ldkv] = k|v, out [B*Ntok, ldo], all bf16 -- in practice q and kv are strided views of one
+ *     [B*Ntok, 3C] q|k|v matrix (ldq = ldkv = 3C); the same stride and alignment rules as the masked form;
+ *   - rounding points of cs_attn_fwd: fp32 scores, exp2 of the scaled difference to the row maximum, P rounded to bf16 before P.V, an fp32
+ *     row sum of the unrounded exponentials, one rounding of the output to bf16; row 0 of a sequence is its v row 0 bit for bit;
+ *   - bit-reproducible (no atomics); rows past a sequence's end are never read from the next sequence or past the tensors.
+ * Every violation returns -1 with a cs_last_error() text. */
 int cs_attn_query_fwd(const void* q, const void* kv, const unsigned char* allow, void* out, float* lse, int B, int Q, int Ntok, int H,
                       int ldq, int ldkv, int ldo, float scale, cs_stream_t stream);
 /* cs_attn_fwd that also emits stats_part [H][B*Ntok][2] f32 = per head (sum, sum of squares) of each output row's 64 values. */
