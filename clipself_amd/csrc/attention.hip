@@ -254,13 +254,14 @@ __device__ __forceinline__ bf16x8 pack8_swapped(const f32x16& a, int c2) {
     return out.v;
 }
 
+template <bool ROPE = true>
 __device__ __forceinline__ void load_q_frags(const AttnArgs& p, const float* rt, size_t rowbase, int qc, int h, int hf, bf16x8 (&qf)[4]) {
     U128 t[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) t[ks].u = *(const uint4*)(p.qkv + (rowbase + qc) * p.ldqkv + h * HD + ks * 16 + hf * 8);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        if (qc > 0) rope8_lds(t[ks], rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
+        if (ROPE && qc > 0) rope8_lds(t[ks], rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
         qf[ks] = t[ks].h;
     }
 }
@@ -277,7 +278,11 @@ __device__ __forceinline__ void load_q_frags(const AttnArgs& p, const float* rt,
 // The same values reach the same MFMAs in both modes: bit-identical outputs.
 // (Tried and removed, round 6: V^T images with the key blocks ROTATED instead of XOR-permuted -- [64][224] rotated by the dim chunk in
 // attn_fwd8_kernel, 1 % slower; [64][200] for the four-wave forward, a tie.  profiles/r06_c_attention_pipes.md)
-template <int CH, bool TAIL, bool VROW = false>
+// PIN (attn_fwd8_kernel<true, false>, the 14x14 grid without rotary tables): the row sum is brought up to date HERE.  Left alone, hipcc sinks
+// the whole chain of l updates of the kernel's three attend_chunk calls below the last one and keeps every chunk's two partial sums alive until
+// then -- one register more than the 128 of that kernel hold (the rotary form spills one dword to scratch for it; with PIN: 124 VGPRs, no
+// scratch).  Same operations on the same values.
+template <int CH, bool TAIL, bool VROW = false, bool PIN = false>
 __device__ __forceinline__ void attend_chunk(const char* Kl, const __bf16* Vt, const bf16x8 (&qf)[4], int key0, int Ntok, float sl2,
                                              int lane, bool first, float& m, float& l, f32x16 (&o)[2], int t0 = 0) {
     const int hf = lane >> 5, l31 = lane & 31;
@@ -346,6 +351,7 @@ __device__ __forceinline__ void attend_chunk(const char* Kl, const __bf16* Vt, c
     rs += __shfl_xor(rs, 32, 64);
     l = l * alpha + rs;
     m = m_new;
+    if constexpr (PIN) asm volatile("" : "+v"(l));
     if (!first) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) { o[0][e] *= alpha; o[1][e] *= alpha; }
@@ -415,13 +421,14 @@ __device__ __forceinline__ void store_o(const AttnArgs& p, size_t rowbase, int q
 // registers (16 per tile) leave room for the prefetch.
 // (Tried and removed: round 1's synchronous attn_fwd_kernel -- stage a chunk, barrier, attend it -- 219-248 vs 202-206 us at the recipe's
 // 4097 tokens.  profiles/r05_c_attention_restaged_bench.txt)
-template <int CH, int CH1>
+// ROPE = false (cos_t == sin_t == NULL, the family without rotary embedding): no tables in LDS, q and k rows reach the MFMAs as loaded.
+template <int CH, int CH1, bool ROPE = true>
 __global__ __launch_bounds__(512, 2) void attn_fwd2_kernel(AttnArgs p) {
     constexpr int CHK = CH * 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kl = smem;
     char* Vl = smem + CHK * 128;
-    float* rt = (float*)(smem + 2 * CHK * 128);          // compact RoPE tables [4][g][32]
+    float* rt = (float*)(smem + 2 * CHK * 128);          // compact RoPE tables [4][g][32] (ROPE only)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5, l31 = lane & 31;
     const RowBlock rb = map_block(p, 8);
@@ -434,15 +441,17 @@ __global__ __launch_bounds__(512, 2) void attn_fwd2_kernel(AttnArgs p) {
     RowRegs<CHK> kr, vr;
     kr.load(p.qkv, rowbase, p.ldqkv, C + h * HD, 0, p.Ntok, tid);
     vr.load(p.qkv, rowbase, p.ldqkv, 2 * C + h * HD, 0, p.Ntok, tid);
-    load_rope_tables<512>(rt, p.cos_t, p.sin_t, p.grid, tid);
-    __syncthreads();
+    if constexpr (ROPE) {
+        load_rope_tables<512>(rt, p.cos_t, p.sin_t, p.grid, tid);
+        __syncthreads();
+    }
     bf16x8 qf[4];
-    load_q_frags(p, rt, rowbase, qc, h, hf, qf);
+    load_q_frags<ROPE>(p, rt, rowbase, qc, h, hf, qf);
     float m = -INFINITY, l = 0.f;
     f32x16 o[2] = {zero16(), zero16()};
     for (int key0 = 0; key0 < p.Ntok; key0 += CHK) {
         if (key0) __syncthreads();
-        kr.template store<true>(Kl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
+        kr.template store<ROPE>(Kl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
         vr.template store<false>(Vl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
         __syncthreads();
         if (key0 + CHK < p.Ntok) {
@@ -471,13 +480,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd2_kernel(AttnArgs p) {
 // (Tried and removed: round 5's V row-major in LDS + ds_read_b64_tr_b16 fragments -- bit-identical, 2 % slower per 2048-crop launch,
 // profiles/r05_h_fwd8_row_major_v.txt; round 6's four waves per unit and three units per CU -- bit-identical, a tie,
 // 424-426 vs 419-422 us per 1024-crop launch, profiles/r06_c_attention_pipes.md.)
-template <bool TAIL>
+// ROPE = false (cos_t == sin_t == NULL): no table loads, no table region in LDS, no barrier ahead of the K staging, no rotation.
+template <bool TAIL, bool ROPE = true>
 __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
     constexpr int CH = 7, CHK = CH * 32, NT = 512;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kl = smem;
     __bf16* Vt = (__bf16*)(smem + CHK * 128);
-    float* rt = (float*)(smem + CHK * 128 + HD * VT_LD * 2);      // compact RoPE tables [4][g][32]
+    float* rt = (float*)(smem + CHK * 128 + HD * VT_LD * 2);      // compact RoPE tables [4][g][32] (ROPE only)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5, l31 = lane & 31;
     const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
     const int C = p.H * HD;
@@ -486,7 +496,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
     const int last = p.Ntok - 1;
     // every global load of the workgroup ahead of the first dependent instruction: tables (oldest: vmcnt retires in order), K, V, Q
     float tab[4];
-    {
+    if constexpr (ROPE) {
         const int i = min(tid, p.grid * 32 - 1), r = i >> 5, d = i & 31;       // g * 32 <= 448 entries per table
         tab[0] = p.cos_t[(size_t)(r * p.grid) * HD + d];
         tab[1] = p.sin_t[(size_t)(r * p.grid) * HD + d];
@@ -512,18 +522,20 @@ __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
     const int q0 = wave * 32, q = q0 + l31, qc = min(q, last);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qraw[ks].u = *(const uint4*)(p.qkv + (rowbase + qc) * p.ldqkv + h * HD + ks * 16 + hf * 8);
-    if (tid < p.grid * 32) {
-        rt[tid] = tab[0];
-        rt[(p.grid << 5) + tid] = tab[1];
-        rt[(2 * p.grid << 5) + tid] = tab[2];
-        rt[(3 * p.grid << 5) + tid] = tab[3];
+    if constexpr (ROPE) {
+        if (tid < p.grid * 32) {
+            rt[tid] = tab[0];
+            rt[(p.grid << 5) + tid] = tab[1];
+            rt[(2 * p.grid << 5) + tid] = tab[2];
+            rt[(3 * p.grid << 5) + tid] = tab[3];
+        }
+        __syncthreads();
     }
-    __syncthreads();
 #pragma unroll
     for (int it = 0; it < KI; ++it) {          // K: rotate + swizzled LDS image
         const int idx = tid + it * NT, r = idx >> 3, c = idx & 7;
         if (idx < CHK * 8) {
-            if (r > 0 && r < p.Ntok && !ATT_ABL(p, 2)) rope8_lds(kr[it], rt, p.grid, p.inv_grid, r, c);
+            if (ROPE && r > 0 && r < p.Ntok && !ATT_ABL(p, 2)) rope8_lds(kr[it], rt, p.grid, p.inv_grid, r, c);
             *(uint4*)(Kl + k_off(r, c)) = kr[it].u;
         }
     }
@@ -542,17 +554,17 @@ __global__ __launch_bounds__(512, 4) void attn_fwd8_kernel(AttnArgs p) {
     bf16x8 qf[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        if (qc > 0 && !ATT_ABL(p, 2)) rope8_lds(qraw[ks], rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
+        if (ROPE && qc > 0 && !ATT_ABL(p, 2)) rope8_lds(qraw[ks], rt, p.grid, p.inv_grid, qc, ks * 2 + hf);
         qf[ks] = qraw[ks].h;
     }
     float m = -INFINITY, l = 0.f;
     f32x16 o[2] = {zero16(), zero16()};
     if (ATT_ABL(p, 1)) { l = 1.f; m = 0.f; o[0][0] = bf2f(qf[0][0]); }
     else if (TAIL) {                       // 192 < Ntok <= 224 (the 14x14 + CLS grid): two full chunks and the ragged last tile
-        attend_chunk<3, false>(Kl, Vt, qf, 0, p.Ntok, sl2, lane, true, m, l, o, 0);
-        attend_chunk<3, false>(Kl, Vt, qf, 96, p.Ntok, sl2, lane, false, m, l, o, 3);
-        attend_chunk<1, true>(Kl, Vt, qf, 192, p.Ntok, sl2, lane, false, m, l, o, 6);
-    } else {
+        attend_chunk<3, false, false, !ROPE>(Kl, Vt, qf, 0, p.Ntok, sl2, lane, true, m, l, o, 0);
+        attend_chunk<3, false, false, !ROPE>(Kl, Vt, qf, 96, p.Ntok, sl2, lane, false, m, l, o, 3);
+        attend_chunk<1, true, false, !ROPE>(Kl, Vt, qf, 192, p.Ntok, sl2, lane, false, m, l, o, 6);
+    } else {                               // (PIN buys nothing here: this form keeps one q fragment in scratch with or without it)
         attend_chunk<3, false>(Kl, Vt, qf, 0, p.Ntok, sl2, lane, true, m, l, o, 0);
         if (p.Ntok > 96) attend_chunk<3, false>(Kl, Vt, qf, 96, p.Ntok, sl2, lane, false, m, l, o, 3);
         if (p.Ntok > 192) attend_chunk<1, false>(Kl, Vt, qf, 192, p.Ntok, sl2, lane, false, m, l, o, 6);
@@ -791,7 +803,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnArgs p) {
 // every one of its 17 row blocks at the recipe's 4097 tokens -- a fifth of the kernels' VALU instructions.  Same rotation arithmetic, same bits.
 // Launched as <CH, true, false> (one chunk, rotated from the LDS tables) and <CH, false, true> (several chunks, prepass).  (Tried and removed:
 // several chunks without the prepass -- 5.5 % slower, 531 vs 502 us at 2 x 12 x 4097.  profiles/r06_f_long_sequence_prepass_ab.txt)
-template <int CH, bool SINGLE, bool PRE = false>
+// ROPE = false (cos_t == sin_t == NULL, the family without rotary embedding): no tables, no rotation on load, no inverse rotation of the
+// gradients; the PRE form then reads q | k from the q|k|v matrix itself (p.qk = p.qkv, no prepass).
+template <int CH, bool SINGLE, bool PRE = false, bool ROPE = true>
 __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnArgs p) {
     constexpr int CHK = CH * 32, NT = 512, NW = 8;
     constexpr bool PF = true;
@@ -819,10 +833,12 @@ __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnA
     if constexpr (PRE) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(p.qk + (rowbase + qc) * p.ldqk + h * HD + ks * 16 + hf * 8);
-    } else {
+    } else if constexpr (ROPE) {
         load_rope_tables<NT>(rt, p.cos_t, p.sin_t, p.grid, tid);
         __syncthreads();
         load_q_frags(p, rt, rowbase, qc, h, hf, qf);
+    } else {
+        load_q_frags<false>(p, rt, rowbase, qc, h, hf, qf);
     }
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) dof[ks] = *(const bf16x8*)(p.dout + (rowbase + qc) * p.ldo + h * HD + ks * 16 + hf * 8);
@@ -843,7 +859,7 @@ __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnA
 
     for (int key0 = 0; key0 < (SINGLE ? 1 : p.Ntok); key0 += CHK) {
         if (key0) __syncthreads();                     // every wave is done with the previous chunk's images
-        kr.template store<!PRE, true>(Kl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
+        kr.template store<!PRE && ROPE, true>(Kl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
         vr.template store<false>(Vl, rt, p.grid, p.inv_grid, key0, p.Ntok, tid);
         __syncthreads();
         if (!SINGLE && PF && key0 + CHK < p.Ntok) {    // the next chunk's rows travel while this one is consumed
@@ -897,12 +913,12 @@ __global__ __launch_bounds__(512, SINGLE ? 4 : 2) void attn_bwd_dq2_kernel(AttnA
     }
     if (wave_active && q < p.Ntok) {
         const size_t pos = (size_t)(q > 0 ? q - 1 : 0) * HD;
-        store_grad_tile(dq, p.out + (rowbase + q) * p.ldqkv + h * HD, q > 0, p.cos_t + pos, p.sin_t + pos, hf);
+        store_grad_tile(dq, p.out + (rowbase + q) * p.ldqkv + h * HD, ROPE && q > 0, p.cos_t + pos, p.sin_t + pos, hf);
     }
 }
 
 // dK, dV: wave = 32 keys, loops over query chunks.  S = Q K^T (lane = key, registers = queries);  dV^T += dO^T . P ;  dK^T += Q^T . dS
-template <int CH, bool SINGLE, bool PRE = false>
+template <int CH, bool SINGLE, bool PRE = false, bool ROPE = true>
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {       // 64 + 32 + 32 accumulator / operand registers: no 128-register form
     constexpr int CHQ = CH * 32, NT = 512, NW = 8;
     constexpr bool PF = true;
@@ -911,7 +927,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {    
     char* Gl = smem + CHQ * 128;
     float* lse_s = (float*)(smem + 2 * CHQ * 128);
     float* dsum_s = lse_s + CHQ;
-    float* rt = dsum_s + CHQ;
+    float* rt = dsum_s + CHQ;                          // (!PRE && ROPE only)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hf = lane >> 5, l31 = lane & 31;
     const RowBlock rb = map_block(p, NW);
@@ -937,7 +953,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {    
         }
     };
     load_stats(0);
-    if constexpr (!PRE) {
+    if constexpr (!PRE && ROPE) {
         load_rope_tables<NT>(rt, p.cos_t, p.sin_t, p.grid, tid);
         __syncthreads();
     }
@@ -952,7 +968,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {    
         }
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            if (!PRE && kc > 0) rope8_lds(t[ks], rt, p.grid, p.inv_grid, kc, ks * 2 + hf);
+            if (!PRE && ROPE && kc > 0) rope8_lds(t[ks], rt, p.grid, p.inv_grid, kc, ks * 2 + hf);
             kf[ks] = t[ks].h;
         }
     }
@@ -969,7 +985,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {    
 
     for (int q0 = 0; q0 < (SINGLE ? 1 : p.Ntok); q0 += CHQ) {
         if (q0) __syncthreads();
-        qr.template store<!PRE>(Ql, rt, p.grid, p.inv_grid, q0, p.Ntok, tid);
+        qr.template store<!PRE && ROPE>(Ql, rt, p.grid, p.inv_grid, q0, p.Ntok, tid);
         gr.template store<false>(Gl, rt, p.grid, p.inv_grid, q0, p.Ntok, tid);
         if (tid < CHQ) { lse_s[tid] = lse_r; dsum_s[tid] = dsum_r; }
         __syncthreads();
@@ -1022,7 +1038,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv2_kernel(AttnArgs p) {    
     if (wave_active && key < p.Ntok) {
         const size_t pos = (size_t)(key > 0 ? key - 1 : 0) * HD;
         __bf16* row = p.out + (rowbase + key) * p.ldqkv + h * HD;
-        store_grad_tile(dk, row + C, key > 0, p.cos_t + pos, p.sin_t + pos, hf);
+        store_grad_tile(dk, row + C, ROPE && key > 0, p.cos_t + pos, p.sin_t + pos, hf);
         store_grad_tile(dv, row + 2 * C, false, nullptr, nullptr, hf);
     }
 }
@@ -1058,6 +1074,13 @@ void set_lds(K kernel, size_t bytes) { (void)hipFuncSetAttribute((const void*)ke
 int check_common(const char* who, int B, int Ntok, int H, int ldqkv, int ldo) {
     CS_CHECK_ARG(B > 0 && Ntok > 1 && H > 0, "%s: bad shape B=%d N=%d H=%d", who, B, Ntok, H);
     CS_CHECK_ARG(ldqkv % 8 == 0 && ldo % 8 == 0 && ldqkv >= 3 * H * HD && ldo >= H * HD, "%s: bad leading dimensions", who);
+    return 0;
+}
+
+// cos_t == NULL && sin_t == NULL selects the form without rotary embedding (the OpenAI-CLIP ViT family); one NULL table is an argument error
+int check_tables(const char* who, const float* cos_t, const float* sin_t) {
+    CS_CHECK_ARG((cos_t == nullptr) == (sin_t == nullptr), "%s: cos_t and sin_t are given together, or both NULL (no rotary embedding); got %s only",
+                 who, cos_t ? "cos_t" : "sin_t");
     return 0;
 }
 
@@ -1493,15 +1516,21 @@ __global__ __launch_bounds__(NT * UPW * 64) void attn_causal_kernel(CausalArgs p
 // C ABI ------------------------------------------------------------------------------------------
 // qkv [B*N, ldqkv] bf16 (q|k|v, un-rotated, bias already added); cos/sin [(N-1), 64] f32; out [B*N, ldo] bf16;
 // lse [B*H, N] f32 or null.  Head dim fixed at 64 (both EVA02 towers).
+// cos_t == sin_t == NULL: no rotary embedding (the OpenAI-CLIP ViT family) -- any Ntok > 1, no tables in LDS, no rotation; the outputs equal
+// those of identity tables (cos 1, sin 0) by value.  Exactly one NULL table is an argument error.
 static int attn_fwd_impl(const void* qkv, const float* cos_t, const float* sin_t, void* out, float* lse, float* stats_part, int B, int Ntok,
                          int H, int ldqkv, int ldo, float scale, hipStream_t stream) {
-    if (check_common("cs_attn_fwd", B, Ntok, H, ldqkv, ldo)) return -1;
+    if (check_common("cs_attn_fwd", B, Ntok, H, ldqkv, ldo) || check_tables("cs_attn_fwd", cos_t, sin_t)) return -1;
+    const bool rope = cos_t != nullptr;
     AttnArgs a{};
     a.qkv = (const __bf16*)qkv; a.cos_t = cos_t; a.sin_t = sin_t; a.out = (__bf16*)out; a.lse_out = lse;
     a.stats_part = stats_part; a.Mtot = (long)B * Ntok;
-    int g = (int)(sqrtf((float)(Ntok - 1)) + 0.5f);
-    CS_CHECK_ARG(g * g == Ntok - 1, "cs_attn_fwd: Ntok - 1 = %d is not a square token grid (the RoPE tables are read separably)", Ntok - 1);
-    a.grid = g; a.inv_grid = 1.f / (float)g;
+    int g = 0;                                     // without tables nothing needs a token grid: any Ntok > 1
+    if (rope) {
+        g = (int)(sqrtf((float)(Ntok - 1)) + 0.5f);
+        CS_CHECK_ARG(g * g == Ntok - 1, "cs_attn_fwd: Ntok - 1 = %d is not a square token grid (the RoPE tables are read separably)", Ntok - 1);
+        a.grid = g; a.inv_grid = 1.f / (float)g;
+    }
 #ifdef CS_ABLATION_SWITCHES
     static const int dbg_env = getenv("CS_ATTN_DBG") ? atoi(getenv("CS_ATTN_DBG")) : 0;
     a.dbg = dbg_env;
@@ -1515,17 +1544,25 @@ static int attn_fwd_impl(const void* qkv, const float* cos_t, const float* sin_t
     if (Ntok <= CH * 32) {
         // whole sequence in one LDS image: eight waves, one query tile each, two workgroups (16 waves) per CU; when only the last key tile is
         // ragged (Ntok > 32 (CH - 1): the 14x14 grid), the variant whose ragged-tile code exists once
-        static bool once = (set_lds(attn_fwd8_kernel<false>, 160 * 1024), set_lds(attn_fwd8_kernel<true>, 160 * 1024), true);
+        static bool once = (set_lds(attn_fwd8_kernel<false>, 160 * 1024), set_lds(attn_fwd8_kernel<true>, 160 * 1024),
+                            set_lds(attn_fwd8_kernel<false, false>, 160 * 1024), set_lds(attn_fwd8_kernel<true, false>, 160 * 1024), true);
         (void)once;
-        if (Ntok > (CH - 1) * 32) hipLaunchKernelGGL((attn_fwd8_kernel<true>), dim3(1, B * H), dim3(512), lds, stream, a);
-        else hipLaunchKernelGGL((attn_fwd8_kernel<false>), dim3(1, B * H), dim3(512), lds, stream, a);
+        const bool tail = Ntok > (CH - 1) * 32;
+        if (rope) {
+            if (tail) hipLaunchKernelGGL((attn_fwd8_kernel<true>), dim3(1, B * H), dim3(512), lds, stream, a);
+            else hipLaunchKernelGGL((attn_fwd8_kernel<false>), dim3(1, B * H), dim3(512), lds, stream, a);
+        } else {
+            if (tail) hipLaunchKernelGGL((attn_fwd8_kernel<true, false>), dim3(1, B * H), dim3(512), lds, stream, a);
+            else hipLaunchKernelGGL((attn_fwd8_kernel<false, false>), dim3(1, B * H), dim3(512), lds, stream, a);
+        }
     } else {
-        static bool once = (set_lds(attn_fwd2_kernel<CH, 4>, 160 * 1024), true);
+        static bool once = (set_lds(attn_fwd2_kernel<CH, 4>, 160 * 1024), set_lds(attn_fwd2_kernel<CH, 4, false>, 160 * 1024), true);
         (void)once;
         const size_t lds2 = (size_t)2 * CH * 32 * 128 + (size_t)4 * g * 32 * sizeof(float);
         dim3 grid2;
         set_schedule(a, B, Ntok, H, grid2);
-        hipLaunchKernelGGL((attn_fwd2_kernel<CH, 4>), grid2, dim3(512), lds2, stream, a);
+        if (rope) hipLaunchKernelGGL((attn_fwd2_kernel<CH, 4>), grid2, dim3(512), lds2, stream, a);
+        else hipLaunchKernelGGL((attn_fwd2_kernel<CH, 4, false>), grid2, dim3(512), lds2, stream, a);
     }
     CS_LAUNCH_CHECK();
     return 0;
@@ -1580,19 +1617,39 @@ static int attn_bwd_image(const void* qkv, const void* o, const void* dout, cons
     dim3 grid((Ntok + 255) / 256, B * H), block(512);
     constexpr int CH = 7;
     constexpr int CHK = CH * 32, VLD = CHK + 4;
-    const int g = (int)(sqrtf((float)(Ntok - 1)) + 0.5f);
+    const bool tables = cos_t != nullptr;
+    const int g = tables ? (int)(sqrtf((float)(Ntok - 1)) + 0.5f) : 0;
     // the round-1 kernels (transposed images, RoPE from the full global tables): the A/B switch, read per launch -- and the form that serves a
-    // token count that is not a square grid + 1 (the re-staged kernels read the tables separably, row part | column part)
-    const bool v1 = getenv("CS_ATTN_BWD_V1") != nullptr || g * g != Ntok - 1;
+    // token count that is not a square grid + 1 (the re-staged kernels read the tables separably, row part | column part).  Both concern the
+    // table form only: without tables (cos_t == sin_t == NULL) every token count runs the re-staged kernels.
+    const bool v1 = tables && (getenv("CS_ATTN_BWD_V1") != nullptr || g * g != Ntok - 1);
     if (!v1) {
-        a.grid = g; a.inv_grid = 1.f / (float)g;
+        a.grid = g; a.inv_grid = tables ? 1.f / (float)g : 0.f;
         const size_t rope = (size_t)4 * g * 32 * sizeof(float);
         const size_t lds_dq = (size_t)2 * CHK * 128 + rope, lds_dkv = (size_t)2 * CHK * 128 + (size_t)2 * CHK * sizeof(float) + rope;
         CS_CHECK_ARG(lds_dkv <= 160 * 1024, "cs_attn_bwd: token grid %d too large for the LDS RoPE tables", g);
         static bool once = (set_lds(attn_bwd_dq2_kernel<CH, true>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, true>, 160 * 1024),
-                            set_lds(attn_bwd_dq2_kernel<CH, false, true>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, false, true>, 160 * 1024), true);
+                            set_lds(attn_bwd_dq2_kernel<CH, false, true>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, false, true>, 160 * 1024),
+                            set_lds(attn_bwd_dq2_kernel<CH, true, false, false>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, true, false, false>, 160 * 1024),
+                            set_lds(attn_bwd_dq2_kernel<CH, false, true, false>, 160 * 1024), set_lds(attn_bwd_dkv2_kernel<CH, false, true, false>, 160 * 1024),
+                            true);
         (void)once;
-        if (Ntok <= CHK) {
+        if (!tables) {
+            // no rotation: the one-chunk kernels skip the tables, and the several-chunk (PRE) kernels read q | k where rope_qk_kernel would have
+            // copied them from -- the q | k columns of qkv itself -- so the prepass and its workspace image are not touched
+            if (Ntok <= CHK) {
+                hipLaunchKernelGGL((attn_bwd_dq2_kernel<CH, true, false, false>), grid, block, lds_dq, stream, a);
+                CS_LAUNCH_CHECK();
+                hipLaunchKernelGGL((attn_bwd_dkv2_kernel<CH, true, false, false>), grid, block, lds_dkv, stream, a);
+            } else {
+                dim3 grid2;
+                set_schedule(a, B, Ntok, H, grid2);
+                a.qk = (const __bf16*)qkv; a.ldqk = ldqkv;
+                hipLaunchKernelGGL((attn_bwd_dq2_kernel<CH, false, true, false>), grid2, block, lds_dq, stream, a);
+                CS_LAUNCH_CHECK();
+                hipLaunchKernelGGL((attn_bwd_dkv2_kernel<CH, false, true, false>), grid2, block, lds_dkv, stream, a);
+            }
+        } else if (Ntok <= CHK) {
             hipLaunchKernelGGL((attn_bwd_dq2_kernel<CH, true>), grid, block, lds_dq, stream, a);
             CS_LAUNCH_CHECK();
             hipLaunchKernelGGL((attn_bwd_dkv2_kernel<CH, true>), grid, block, lds_dkv, stream, a);
@@ -1627,10 +1684,11 @@ static int attn_bwd_image(const void* qkv, const void* o, const void* dout, cons
 // o, dout [B*N, ldo] bf16; lse from the forward; dqkv [B*N, ldqkv] bf16 receives d(q|k|v) w.r.t. the *un-rotated* q,k.
 // extra (nullable): the Q extra query rows per image of cs_attn_query_fwd.  Their dK / dV are added to the k|v columns of dqkv after the image
 // rows' kernels, their dq goes to extra->dq; with extra, o / dout / lse may all be NULL (no image rows: dqkv = [0 | dK | dV]).
+// cos_t == sin_t == NULL: no rotary embedding, as in cs_attn_fwd -- any Ntok > 1 on the re-staged kernels, no rope_qk_kernel prepass.
 extern "C" int cs_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, const float* cos_t, const float* sin_t,
                            void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, const cs_attn_extra* extra,
                            hipStream_t stream) {
-    if (check_common("cs_attn_bwd", B, Ntok, H, ldqkv, ldo)) return -1;
+    if (check_common("cs_attn_bwd", B, Ntok, H, ldqkv, ldo) || check_tables("cs_attn_bwd", cos_t, sin_t)) return -1;
     if (extra == nullptr) return attn_bwd_image(qkv, o, dout, lse, cos_t, sin_t, dqkv, workspace, B, Ntok, H, ldqkv, ldo, scale, stream);
     const cs_attn_extra& e = *extra;
     const bool image = o != nullptr || dout != nullptr || lse != nullptr;
@@ -1685,7 +1743,8 @@ static int attn_cls_launch(const void* q, const void* kv, const float* cos_t, co
 // (un-rotated, bias added); out [B, ldo] bf16 = the CLS row of softmax(q k^T * scale) v.
 extern "C" int cs_attn_cls_fwd(const void* q, const void* kv, const float* cos_t, const float* sin_t, void* out, int B, int Ntok, int H,
                                int ldq, int ldkv, int ldo, float scale, hipStream_t stream) {
-    CS_CHECK_ARG(q && kv && cos_t && sin_t && out, "cs_attn_cls_fwd: null pointer");
+    CS_CHECK_ARG(q && kv && out, "cs_attn_cls_fwd: null pointer");
+    if (check_tables("cs_attn_cls_fwd", cos_t, sin_t)) return -1;
     CS_CHECK_ARG(B > 0 && Ntok > 1 && H > 0, "cs_attn_cls_fwd: bad sizes B=%d Ntok=%d H=%d", B, Ntok, H);
     CS_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldq >= H * HD && ldkv >= 2 * H * HD && ldo >= H * HD,
                  "cs_attn_cls_fwd: row strides must be multiples of 8 and cover the heads (ldq=%d ldkv=%d ldo=%d)", ldq, ldkv, ldo);

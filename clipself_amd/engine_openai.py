@@ -17,11 +17,13 @@ does each stage (paths under /root/reference/src/open_clip/):
 The frozen teacher runs TowerEngine.encode_image like the EVA02 one: CLS-query-only last block, ln_1 / ln_2 folded into the in_proj / c_fc
 GEMMs with the residual GEMMs emitting the bf16 copy and the row statistics of the stream (`_teacher_block_folded`).
 
-Differences to the EVA02 schedule: no RoPE (the attention kernels get identity tables), no sub-LayerNorms, `proj` is a bias-free
+Differences to the EVA02 schedule: no RoPE (the attention kernels run without tables: rope_tables), no sub-LayerNorms, `proj` is a bias-free
 [C,E] matrix kept transposed for the forward GEMM, and the last dense block owns no never-reached *tensor* (q/k are rows of the one
 in_proj_weight parameter, whose gradient rows stay zero -- exactly what autograd hands torch's AdamW).
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -149,7 +151,11 @@ class ClipVitEngine(TowerEngine):
 
     # ------------------------------------------------------------------------------------------ tables
     def rope_tables(self, grid: int):
-        """No rotary embedding in this family: cos = 1, sin = 0 turn the attention kernels' rotation into the identity."""
+        """No rotary embedding in this family.  On a backend that advertises ATTN_NO_ROPE the attention ops get (None, None) -- kernels
+        without tables and without the rotation; elsewhere (the CPU reference), or with CLIPSELF_ATTN_IDENTITY_ROPE=1 (the A/B switch,
+        read per call), cos = 1, sin = 0 turn the rotation into the identity.  Same values either way."""
+        if getattr(self.ops, "ATTN_NO_ROPE", False) and os.environ.get("CLIPSELF_ATTN_IDENTITY_ROPE", "0") in ("", "0"):
+            return None, None
         key = ("rope", grid)
         if key not in self._tables:
             shape = (grid * grid, self.cfg.head_width)

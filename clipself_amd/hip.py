@@ -138,6 +138,7 @@ class HipOps:
     name = "hip"
     ATTN_EXTRA_QUERIES = True           # attn_query_fwd(lse=) / attn_bwd(extra=): mask-attention pooling is differentiable on this backend
     ATTN_CAUSAL = True                  # attn_query_fwd(allow=None): causal self-attention, what the text tower (encode_text) runs on
+    ATTN_NO_ROPE = True                 # attn_fwd / attn_fwd_stats / attn_cls_fwd / attn_bwd(cos=None, sin=None): no rotary embedding, any Ntok > 1
 
     def __init__(self):
         self.lib = load_library()
@@ -373,9 +374,18 @@ class HipOps:
             seen.clear()
         seen.add(key)
 
+    @staticmethod
+    def _no_rope(cos, sin, who) -> bool:
+        """True for cos is None and sin is None: the form without rotary embedding (NULL tables in the C ABI; the outputs equal those of
+        identity tables by value).  One table without the other is an error here, before any launch."""
+        if (cos is None) != (sin is None):
+            raise ValueError(f"{who}: cos and sin are given together, or both None (no rotary embedding)")
+        return cos is None
+
     def attn_fwd_stats(self, qkv, cos, sin, out, lse, stats_part, B, Ntok, H, scale):
         self._chk(qkv, cos, sin, out, lse, stats_part)
-        self._check_rope_tables(cos, sin, Ntok)
+        if not self._no_rope(cos, sin, "attn_fwd_stats"):
+            self._check_rope_tables(cos, sin, Ntok)
         assert stats_part.is_contiguous() and tuple(stats_part.shape) == (H, B * Ntok, 2)
         self._ok(self.lib.cs_attn_fwd_stats(_p(qkv), _p(cos), _p(sin), _p(out), _p(lse), _p(stats_part), B, Ntok, H, qkv.stride(0),
                                             out.stride(0), scale, self._stream()), "cs_attn_fwd_stats")
@@ -461,12 +471,14 @@ class HipOps:
 
     def attn_fwd(self, qkv, cos, sin, out, lse, B, Ntok, H, scale):
         self._chk(qkv, cos, sin, out, lse)
-        self._check_rope_tables(cos, sin, Ntok)
+        if not self._no_rope(cos, sin, "attn_fwd"):
+            self._check_rope_tables(cos, sin, Ntok)
         self._ok(self.lib.cs_attn_fwd(_p(qkv), _p(cos), _p(sin), _p(out), _p(lse), B, Ntok, H, qkv.stride(0), out.stride(0),
                                       scale, self._stream()), "cs_attn_fwd")
 
     def attn_cls_fwd(self, q, kv, cos, sin, out, B, Ntok, H, scale):
         self._chk(q, kv, cos, sin, out)
+        self._no_rope(cos, sin, "attn_cls_fwd")
         self._ok(self.lib.cs_attn_cls_fwd(_p(q), _p(kv), _p(cos), _p(sin), _p(out), B, Ntok, H, q.stride(0), kv.stride(0),
                                           out.stride(0), scale, self._stream()), "cs_attn_cls_fwd")
 
@@ -500,8 +512,10 @@ class HipOps:
         seen.add(key)
 
     def attn_bwd(self, qkv, o, dout, lse, cos, sin, dqkv, workspace, B, Ntok, H, scale, extra=None):
-        """extra: dict(q, o, dout, lse, allow, dq, Q) -- the extra query rows of the launch (cs_attn_extra); o / dout / lse may then be None."""
+        """extra: dict(q, o, dout, lse, allow, dq, Q) -- the extra query rows of the launch (cs_attn_extra); o / dout / lse may then be None.
+        cos = sin = None: no rotary embedding (with extra rows the tables must be the identity or None, which mean the same)."""
         self._chk(qkv, o, dout, lse, cos, sin, dqkv, workspace)
+        no_rope = self._no_rope(cos, sin, "attn_bwd")
         assert qkv.stride(0) == dqkv.stride(0)
         if extra is None:
             assert o.stride(0) == dout.stride(0)
@@ -510,7 +524,8 @@ class HipOps:
             return
         q, eo, edo, elz, allow, dq, Q = (extra[k] for k in ("q", "o", "dout", "lse", "allow", "dq", "Q"))
         self._chk(q, eo, edo, elz, allow, dq)
-        self._check_identity_tables(cos, sin)
+        if not no_rope:
+            self._check_identity_tables(cos, sin)
         assert (o is None) == (dout is None) == (lse is None), "image rows: o, dout and lse together or not at all"
         assert o is None or o.stride(0) == dout.stride(0)
         assert eo.stride(0) == edo.stride(0) and all(t.stride(1) == 1 for t in (q, eo, edo, dq))

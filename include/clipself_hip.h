@@ -141,12 +141,20 @@ int cs_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, void* 
  * part of grid column i (both come from the same `freqs` tensor, rope.py:134-138) and the two dims of a rotation pair share their entry
  * (`repeat(..., r = 2)`, :137) -- i.e.
  * cos_t[(i*g)*64 + 2j] == cos_t[(i*g)*64 + 2j+1] == cos_t[i*64 + 32 + 2j], same for sin_t.  Identity tables (cos 1, sin 0: the OpenAI-CLIP
- * family) satisfy it.  The Python wrapper (clipself_amd/hip.py) verifies the tables once per tensor and raises otherwise. */
+ * family) satisfy it.  The Python wrapper (clipself_amd/hip.py) verifies the tables once per tensor and raises otherwise.
+ *
+ * cos_t == NULL && sin_t == NULL selects the form WITHOUT ROTARY EMBEDDING (the OpenAI-CLIP ViT family), here and in cs_attn_fwd_stats,
+ * cs_attn_cls_fwd and cs_attn_bwd:
+ *   - q and k rows reach the products as they are: no tables are read or staged, the backward runs no rotation prepass;
+ *   - any Ntok > 1 (nothing needs a square token grid; in cs_attn_bwd every token count runs the same kernels);
+ *   - the rounding points do not move: every output equals that of the same call with identity tables (cos 1, sin 0) by value -- the
+ *     identity rotation rounds bf16 -> fp32 -> x * 1 - y * 0 -> bf16, which is x again (it can only turn -0.0 into +0.0);
+ *   - exactly one of the two being NULL returns -1 with a cs_last_error() text, never a launch. */
 int cs_attn_fwd(const void* qkv, const float* cos_t, const float* sin_t, void* out, float* lse, int B, int Ntok, int H,
                 int ldqkv, int ldo, float scale, cs_stream_t stream);
 /* CLS-query attention for the frozen teacher's last block: VisionTransformer.forward_features returns x[:, 0]
  * (eva_vit_model.py:505-519), so only that query row of the last block is live.  q [B, ldq] bf16 (CLS queries, never rotated);
- * kv [B*Ntok, ldkv] bf16 = k|v; out [B, ldo] bf16. */
+ * kv [B*Ntok, ldkv] bf16 = k|v; out [B, ldo] bf16.  cos_t == sin_t == NULL: keys are not rotated (see cs_attn_fwd; one NULL is an error). */
 int cs_attn_cls_fwd(const void* q, const void* kv, const float* cos_t, const float* sin_t, void* out, int B, int Ntok, int H,
                     int ldq, int ldkv, int ldo, float scale, cs_stream_t stream);
 /* Extra query tokens of the OpenAI-CLIP family's mask-attention pooling: VisionTransformer.mask_attn_pool / _mask_attn_pool
@@ -171,7 +179,8 @@ int cs_attn_cls_fwd(const void* q, const void* kv, const float* cos_t, const flo
  * Every violation returns -1 with a cs_last_error() text. */
 int cs_attn_query_fwd(const void* q, const void* kv, const unsigned char* allow, void* out, float* lse, int B, int Q, int Ntok, int H,
                       int ldq, int ldkv, int ldo, float scale, cs_stream_t stream);
-/* cs_attn_fwd that also emits stats_part [H][B*Ntok][2] f32 = per head (sum, sum of squares) of each output row's 64 values. */
+/* cs_attn_fwd that also emits stats_part [H][B*Ntok][2] f32 = per head (sum, sum of squares) of each output row's 64 values.
+ * cos_t == sin_t == NULL as in cs_attn_fwd. */
 int cs_attn_fwd_stats(const void* qkv, const float* cos_t, const float* sin_t, void* out, float* lse, float* stats_part, int B, int Ntok,
                       int H, int ldqkv, int ldo, float scale, cs_stream_t stream);
 /* The extra query rows ("passengers") of a cs_attn_bwd launch: the Q rows per image that cs_attn_query_fwd ran against the image's keys /
@@ -194,8 +203,12 @@ size_t cs_attn_bwd_workspace(int B, int Ntok, int H, int Q);
  * extra (nullable): the k|v columns of dqkv then hold the image tokens' own gradient plus the passengers' sums (added once, in fp32, after
  * the image rows' kernels; the q columns are not touched by them) and extra->dq receives the passengers' dq.  With extra, o / dout / lse may
  * all be NULL -- a launch without image rows (the last block of the pooling, whose image-token outputs nobody consumes): dqkv =
- * [0 | passenger dK | passenger dV].  Passengers exist in the family without rotary embedding only: the tables must be the identity then.
- * No atomics: bit-reproducible.  extra == NULL: every output is bit-identical to the call without the argument. */
+ * [0 | passenger dK | passenger dV].  Passengers exist in the family without rotary embedding only: the tables must be the identity then,
+ * or both NULL, which means the same.
+ * No atomics: bit-reproducible.  extra == NULL: every output is bit-identical to the call without the argument.
+ * cos_t == sin_t == NULL (see cs_attn_fwd): no rotation of q / k on load, no inverse rotation of dq / dk, any Ntok > 1, dqkv equal by value
+ * to the call with identity tables; one NULL table is an argument error.  cs_attn_bwd_workspace() cannot see the tables and stays an upper
+ * bound (the rotated q | k image of long sequences is not written in this form). */
 int cs_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, const float* cos_t, const float* sin_t,
                 void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, const cs_attn_extra* extra,
                 cs_stream_t stream);

@@ -2,7 +2,9 @@
 """cs_attn_fwd (with lse) and cs_attn_bwd on a g x g (+CLS) token grid: microseconds per launch and the share of the MFMA peak (forward 4 N^2 d,
 backward 10 N^2 d FLOPs per head), interleaved: the round-1 backward (CS_ATTN_BWD_V1, read per launch; the forward is the current kernel in
 both passes) and the current kernels.
-usage (GPU box): python tools/attn_long_bench.py [images [grid [heads [reps]]]]     e.g. 2 64 12 (the recipe's 4097 tokens), 64 14 12, 16 24 16"""
+usage (GPU box): python tools/attn_long_bench.py [images [grid [heads [reps]]]]     e.g. 2 64 12 (the recipe's 4097 tokens), 64 14 12, 16 24 16
+                 python tools/attn_long_bench.py norope [images [grid [heads [reps [rounds]]]]]: identity tables (cos 1, sin 0) against NULL tables
+                 (no rotary embedding), forward and backward, the same inputs, timed alternately (profiles/attn_norope_bench.md)"""
 import os
 import sys
 from pathlib import Path
@@ -14,6 +16,9 @@ from clipself_amd.hip import HipOps  # noqa: E402
 
 ops = HipOps()
 argv = sys.argv[1:]
+NOROPE = bool(argv) and argv[0] == "norope"
+if NOROPE:
+    argv = argv[1:]
 B = int(argv[0]) if argv else 2
 g = int(argv[1]) if len(argv) > 1 else 64
 H = int(argv[2]) if len(argv) > 2 else 12
@@ -46,6 +51,22 @@ def timed(fn):
 
 
 ffl, bfl = 4.0 * N * N * 64 * B * H, 10.0 * N * N * 64 * B * H
+if NOROPE:
+    rounds = int(argv[4]) if len(argv) > 4 else 5
+    legs = {"identity": (torch.ones_like(cos), torch.zeros_like(sin)), "null": (None, None)}
+    ops.attn_fwd(qkv, None, None, out, lse, B, N, H, 0.125)
+    t = {(k, w): [] for k in legs for w in ("fwd", "bwd")}
+    for r in range(rounds):
+        for k, (c, s) in legs.items():
+            t[k, "fwd"].append(timed(lambda: ops.attn_fwd(qkv, c, s, out, lse, B, N, H, 0.125)))
+            t[k, "bwd"].append(timed(lambda: ops.attn_bwd(qkv, out, dout, lse, c, s, dqkv, ws, B, N, H, 0.125)))
+    for w, fl in (("fwd", ffl), ("bwd", bfl)):
+        i, n = sorted(t["identity", w]), sorted(t["null", w])
+        mi, mn = i[len(i) // 2], n[len(n) // 2]
+        print(f"{B} images x {H} heads x {N} tokens {w} us: identity tables median {mi:.1f} (min {i[0]:.1f} max {i[-1]:.1f}, spread "
+              f"{100 * (i[-1] - i[0]) / mi:.1f} %) | NULL tables median {mn:.1f} (min {n[0]:.1f} max {n[-1]:.1f}) = {fl / mn / 1e6 / PEAK:.3f} of peak | "
+              f"NULL / identity {mn / mi:.3f}", flush=True)
+    sys.exit(0)
 for rnd in range(2):
     for ver in ("v1", "v2"):
         if ver == "v1":

@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """One-GPU timing of the CLIPSelf step on the OpenAI-CLIP ViT family, same batch shape as BASELINE configs[1]:
-usage (GPU box): python tools/openai_vit_bench.py [--extract-type v1|v2] [--steps N] [ViT-B-16 [images [crops [size [plain]]]]]
+usage (GPU box): python tools/openai_vit_bench.py [--extract-type v1|v2] [--steps N] [--crop-size S] [--rope-ab R] [ViT-B-16 [images [crops [size [plain]]]]]
 ("plain" = teacher without the folded LayerNorms / CLS-only last block, the A/B switch of engine_openai.py; --extract-type v1 = the student
-pools every box through an extra query token (mask-attention pooling) instead of the dense map + RoIAlign; profiles/maskattn_train_bench.md)."""
+pools every box through an extra query token (mask-attention pooling) instead of the dense map + RoIAlign; profiles/maskattn_train_bench.md;
+--crop-size: the teacher's crops at another size than the student's image, e.g. `--crop-size 224 ViT-B-16 2 20 1024` = the reference recipe's
+1024^2 student).  env CLIPSELF_ATTN_IDENTITY_ROPE=1: the attention kernels get identity rotary tables instead of none (the A/B switch of
+ClipVitEngine.rope_tables; profiles/attn_norope_bench.md) -- the line printed says which form ran.  --rope-ab R: R rounds of `--steps` steps
+with the switch on, then off, alternately in this process, one line per window and the medians at the end."""
+import os
 import sys
 import time
 from pathlib import Path
@@ -18,12 +23,16 @@ from clipself_amd.training.optim import FlatAdamW  # noqa: E402
 from clipself_amd.training.train import train_step  # noqa: E402
 
 argv = sys.argv[1:]
-EXTRACT, n = "v2", 6
-for flag in ("--extract-type", "--steps"):
+EXTRACT, n, CROP, AB = "v2", 6, 0, 0
+for flag in ("--extract-type", "--steps", "--crop-size", "--rope-ab"):
     if flag in argv:
         i = argv.index(flag)
         if flag == "--steps":
             n = int(argv[i + 1])
+        elif flag == "--crop-size":
+            CROP = int(argv[i + 1])
+        elif flag == "--rope-ab":
+            AB = int(argv[i + 1])
         else:
             EXTRACT = argv[i + 1]
         del argv[i:i + 2]
@@ -47,8 +56,28 @@ student.train(); teacher.eval()
 opt = FlatAdamW(student, lr=1e-5, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.1)
 args = SimpleNamespace(device=dev, precision="amp_bf16", distributed=False, skip_scheduler=True, grad_clip_norm=None, multiscale=False,
                        extract_type=EXTRACT, cosine_weight=1.0)
-batches = [tuple(t.to(dev) for t in synthetic_batch(B, K, S, S, seed=5 + j)) for j in range(2)]
+CROP = CROP or S
+batches = [tuple(t.to(dev) for t in synthetic_batch(B, K, S, CROP, seed=5 + j)) for j in range(2)]
 method = CLIPSelf()
+if AB:
+    SW, step, ms = "CLIPSELF_ATTN_IDENTITY_ROPE", 0, {"1": [], "0": []}
+    for r in range(AB + 1):                                  # round 0 warms both forms up
+        for leg in ("1", "0"):
+            os.environ[SW] = leg
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(n):
+                out, _, _ = train_step(student, method, batches[step % 2], opt, None, step, teacher, args, next_batch=batches[(step + 1) % 2])
+                step += 1
+            torch.cuda.synchronize()
+            if r:
+                ms[leg].append(1e3 * (time.perf_counter() - t0) / n)
+                print(f"round {r} {'identity tables' if leg == '1' else 'no tables      '}: {ms[leg][-1]:.2f} ms/step", flush=True)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    print(f"{MODEL} extract_type={EXTRACT}: {B} images x {K} crops ({CROP}^2) at {S}^2, {AB} rounds of {n} steps: identity tables median {med['1']:.2f} ms/step "
+          f"(min {min(ms['1']):.2f} max {max(ms['1']):.2f}, spread {100 * (max(ms['1']) - min(ms['1'])) / med['1']:.2f} %) | no tables median {med['0']:.2f} "
+          f"(min {min(ms['0']):.2f} max {max(ms['0']):.2f}) | no tables / identity {med['0'] / med['1']:.4f}, loss {float(out['loss'].detach()):.4f}", flush=True)
+    sys.exit(0)
 for i in range(3):
     out, _, _ = train_step(student, method, batches[i % 2], opt, None, i, teacher, args, next_batch=batches[(i + 1) % 2])
 torch.cuda.synchronize()
@@ -63,8 +92,14 @@ pe = 2 * (N - 1) * 3 * p * p * C
 blk = 8 * N * C * C + 4 * N * N * C + 4 * N * C * Hd                 # in_proj + out_proj, attention, c_fc + c_proj
 blk_na = 4 * N * C * C + 4 * N * C * Hd                                # last dense block: value third of in_proj + out_proj, MLP
 blk_cls = 4 * N * C * C + 4 * C * C + 4 * N * C + 4 * C * Hd          # teacher's last block for the CLS query only
-T = pe + (L - 1) * blk + (blk if plain else blk_cls) + 2 * C * E
+if CROP != S:                                                          # the teacher's tower at its own token count
+    Nc = (CROP // p) ** 2 + 1
+    T = (2 * (Nc - 1) * 3 * p * p * C + (L - 1) * (8 * Nc * C * C + 4 * Nc * Nc * C + 4 * Nc * C * Hd)
+         + ((8 * Nc * C * C + 4 * Nc * Nc * C + 4 * Nc * C * Hd) if plain else (4 * Nc * C * C + 4 * C * C + 4 * Nc * C + 4 * C * Hd)) + 2 * C * E)
+else:
+    T = pe + (L - 1) * blk + (blk if plain else blk_cls) + 2 * C * E
 F = K * T + (pe + (L - 1) * blk + blk_na + 2 * (N - 1) * C * E) + 2 * ((L - 1) * blk + blk_na) + 2 * (N - 1) * C * E
-print(f"{MODEL}{' (plain teacher schedule)' if plain else ''} extract_type={EXTRACT}: {B} images x {K} crops at {S}^2: {1e3 * dt:.1f} ms/step, {B / dt:.1f} images/s, "
+tables = "identity rotary tables" if student.visual.engine.rope_tables(g)[0] is not None else "no rotary tables"
+print(f"{MODEL}{' (plain teacher schedule)' if plain else ''} extract_type={EXTRACT}, attention with {tables}: {B} images x {K} crops ({CROP}^2) at {S}^2: {1e3 * dt:.1f} ms/step, {B / dt:.1f} images/s, "
       + (f"{F * B / dt / 1e12:.0f} TFLOP/s of executed matmul FLOPs ({F * B / dt / 2.5e15:.1%} of the 2.5 PFLOP/s MFMA peak), " if EXTRACT == "v2" else "")
       + f"loss {float(out['loss'].detach()):.4f}", flush=True)
