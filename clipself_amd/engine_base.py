@@ -88,6 +88,7 @@ class TowerEngine:
         self._tables = {}
         self._pos_cache = {}
         self.grad = self.exp_avg = self.exp_avg_sq = self.flags = None
+        self.guard = None                      # cs_adamw_step's guard buffer (norm, clip coefficient, applied, skipped steps): first guarded adamw_step
         self.g = {}
         self.wt = {}
         self.first_trainable = cfg.layers      # no block trainable until lock()/unlock is applied
@@ -553,10 +554,22 @@ class TowerEngine:
         return d_dense
 
     # ------------------------------------------------------------------------------------------ optimizer
-    def adamw_step(self, step: int, lr: float, wd: float, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale: float = 1.0):
-        """One flat AdamW launch over every trainable tensor (fp32 master + bf16 shadow refresh), then the W^T shadows."""
+    def adamw_step(self, step: int, lr: float, wd: float, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale: float = 1.0, max_norm=None,
+                   skip_nonfinite: bool = False):
+        """One flat AdamW launch over every trainable tensor (fp32 master + bf16 shadow refresh), then the W^T shadows.
+        max_norm (a number; None or <= 0: no clipping) / skip_nonfinite: the guarded form of cs_adamw_step -- the L2 norm of grad_scale * grad
+        over the active tensors is taken on the device, the gradient enters the update times min(1, max_norm / (norm + 1e-6)), and with
+        skip_nonfinite a step whose norm is Inf or NaN writes nothing.  What follows the launch runs either way: after a skipped step it
+        rewrites the derived copies from unchanged weights."""
+        kw = {}
+        if max_norm is not None or skip_nonfinite:
+            if not getattr(self.ops, "ADAMW_GUARD", False):
+                raise NotImplementedError(f"the '{self.ops.name}' backend has no guarded AdamW step (gradient clipping / non-finite-step skip on the device)")
+            if self.guard is None:
+                self.guard = self.ops.zeros((self.ops.adamw_guard_numel(self.numel),), F32)
+            kw = dict(max_norm=float(max_norm or 0.0), skip_nonfinite=bool(skip_nonfinite), guard=self.guard)
         self.ops.adamw_step(self.master, self.grad, self.exp_avg, self.exp_avg_sq, self.shadow, self.flags,
-                            lr, beta1, beta2, eps, wd, step, grad_scale)
+                            lr, beta1, beta2, eps, wd, step, grad_scale, **kw)
         self.sync_transposed()
         if self._pos_trains():
             self._pos_cache.clear()                # the position table moved: drop the rescaled copies of non-native grids

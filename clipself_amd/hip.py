@@ -19,6 +19,7 @@ _LIB_PATH = Path(os.environ["CLIPSELF_HIP_LIB"]) if os.environ.get("CLIPSELF_HIP
 
 EPI_BF16, EPI_F32, EPI_RESID_F32, EPI_SWIGLU_BF16, EPI_ATOMIC_F32, EPI_PATCH_F32, EPI_RESID_LN_F32, EPI_GELU_BF16, EPI_QGELU_BF16 = range(9)
 DX_BF16, DX_F32_ASSIGN, DX_F32_ACCUM = range(3)
+ADAMW_GUARD_HEAD, ADAMW_GUARD_SPAN = 8, 16384          # CS_ADAMW_GUARD_HEAD / CS_ADAMW_GUARD_SPAN of the header
 
 _vp, _i, _l, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_size_t
 
@@ -74,7 +75,7 @@ SIGNATURES = {
     "cs_num_compute_units": (_i, []),
     "cs_stream_create_cu_mask": (_i, [_i, _i, ctypes.POINTER(_vp)]),
     "cs_stream_destroy": (_i, [_vp]),
-    "cs_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp]),
+    "cs_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _f, _i, _vp, _vp]),
 }
 
 
@@ -138,6 +139,7 @@ class HipOps:
     name = "hip"
     ATTN_EXTRA_QUERIES = True           # attn_query_fwd(lse=) / attn_bwd(extra=): mask-attention pooling is differentiable on this backend
     ATTN_CAUSAL = True                  # attn_query_fwd(allow=None): causal self-attention, what the text tower (encode_text) runs on
+    ADAMW_GUARD = True                  # adamw_step(max_norm=, skip_nonfinite=, guard=): gradient norm, clipping and the non-finite-step skip on the device
     ATTN_NO_ROPE = True                 # attn_fwd / attn_fwd_stats / attn_cls_fwd / attn_bwd(cos=None, sin=None): no rotary embedding, any Ntok > 1
 
     def __init__(self):
@@ -674,7 +676,17 @@ class HipOps:
         self._ok(self.lib.cs_fed_bce_bwd(_p(logits), logits.stride(0), _p(tgt), _p(dz), dz.stride(0), logits.shape[0], ns, temp, weight,
                                          _p(upstream), self._stream()), "cs_fed_bce_bwd")
 
-    def adamw_step(self, p, g, m, v, shadow, flags, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
-        self._chk(p, g, m, v, shadow, flags)
+    @staticmethod
+    def adamw_guard_numel(n: int) -> int:
+        """Floats of the guard buffer of adamw_step for n parameters: the head + one partial sum of squares per span."""
+        return ADAMW_GUARD_HEAD + (int(n) + ADAMW_GUARD_SPAN - 1) // ADAMW_GUARD_SPAN
+
+    def adamw_step(self, p, g, m, v, shadow, flags, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False,
+                   guard=None):
+        """guard (fp32, adamw_guard_numel(n) floats, zeroed once by the caller): the step also leaves the gradient norm, the clip coefficient
+        of max_norm (<= 0: no clipping), applied / skipped and the count of skipped steps in guard[0..3] -- include/clipself_hip.h."""
+        self._chk(p, g, m, v, shadow, flags, guard)
+        if guard is not None:
+            assert guard.dtype == torch.float32 and guard.is_contiguous() and guard.numel() >= self.adamw_guard_numel(p.numel())
         self._ok(self.lib.cs_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(shadow), _p(flags), p.numel(), lr, beta1, beta2, eps, wd,
-                                        step, grad_scale, self._stream()), "cs_adamw_step")
+                                        step, grad_scale, max_norm, int(bool(skip_nonfinite)), _p(guard), self._stream()), "cs_adamw_step")

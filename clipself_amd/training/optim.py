@@ -34,13 +34,29 @@ class FlatAdamW:
         for _, p in self._extra:
             p.grad = None
 
+    def guard_available(self) -> bool:
+        """True when step(max_norm=, skip_nonfinite=) can take the guarded cs_adamw_step: the backend has it, and no parameter outside the
+        flat buffer (logit_scale) holds a gradient -- its gradient would be missing from the norm."""
+        return bool(getattr(self.engine.ops, "ADAMW_GUARD", False)) and all(p.grad is None for _, p in self._extra)
+
     @torch.no_grad()
-    def step(self):
-        self.step_count += 1
+    def step(self, max_norm=None, skip_nonfinite: bool = False):
+        """max_norm: clip the gradient (of the mean over ranks: grad_divisor is applied first) to this L2 norm, as clip_grad_norm_ does.
+        skip_nonfinite: leave weights and moments alone when the gradient norm is Inf or NaN; the step still counts (bias correction)."""
         g0, g1 = self.param_groups
         b1, b2 = g1["betas"]
+        guard = {}
+        if max_norm is not None or skip_nonfinite:
+            if self.guard_available():
+                guard = dict(max_norm=max_norm, skip_nonfinite=skip_nonfinite)
+            elif skip_nonfinite:
+                raise NotImplementedError(f"skip_nonfinite needs the guarded AdamW step, which the '{self.engine.ops.name}' backend lacks "
+                                          "(or a parameter outside the flat buffer holds a gradient)")
+            else:                                        # the torch passage; the buffers hold the SUM over ranks until AdamW divides
+                torch.nn.utils.clip_grad_norm_([p for p in self.model.parameters() if p.grad is not None], max_norm * self.grad_divisor, norm_type=2.0)
+        self.step_count += 1
         self.engine.adamw_step(self.step_count, g1["lr"], g1["weight_decay"], b1, b2, g1["eps"],
-                               grad_scale=1.0 / self.grad_divisor)
+                               grad_scale=1.0 / self.grad_divisor, **guard)
         for name, p in self._extra:                      # scalar stragglers (never have a grad in CLIPSelf)
             if p.grad is None:
                 continue
@@ -51,6 +67,15 @@ class FlatAdamW:
             st["v"].mul_(b2).addcmul_(g, g, value=1 - b2)
             denom = st["v"].sqrt() / math.sqrt(1 - b2 ** st["step"]) + g0["eps"]
             p.addcdiv_(st["m"], denom, value=-g0["lr"] / (1 - b1 ** st["step"]))
+
+    def grad_stats(self):
+        """dict(norm, clip_coef, applied, skipped_total) of the last guarded step, None when none has run.  Reads the device back: for log
+        steps and tests."""
+        guard = self.engine.guard
+        if guard is None:
+            return None
+        norm, coef, applied, skipped = guard[:4].tolist()
+        return dict(norm=norm, clip_coef=coef, applied=bool(applied), skipped_total=int(skipped))
 
     # ---- torch.optim-compatible checkpoint format (src/training/main.py:304-309) ---------------------
     def _indexed(self):

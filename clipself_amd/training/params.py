@@ -39,7 +39,8 @@ _TABLE = [
 ]
 # additions of this build (absent from the reference): synthetic input pipeline for `--train-data synthetic`
 _EXTRA = [("synthetic-steps", _I, 100), ("synthetic-image-size", _I, None), ("teacher-chunk", _I, 2048),
-          ("no-teacher-prefetch", "flag", False)]      # run the frozen teacher inline instead of one batch ahead on a side stream
+          ("no-teacher-prefetch", "flag", False),      # run the frozen teacher inline instead of one batch ahead on a side stream
+          ("skip-nonfinite-steps", "flag", False)]     # leave weights and moments alone on a step whose gradient norm is Inf / NaN (GradScaler's skip)
 
 
 class _KeyValue(argparse.Action):

@@ -1,7 +1,9 @@
 """Training loop with the reference's step order (src/training/train.py:62-165):
    scheduler(step) -> optimizer.zero_grad() -> method(batch, ...) -> total_loss.backward() -> [grad clip]
    -> optimizer.step() -> logit_scale.clamp_(0, ln 100) -> meters / log line (loss, samples/s, lr, logit scale).
-No GradScaler: the engine's bf16/fp32 mix needs none (precision.py).  In data-parallel runs the per-block gradient
+No GradScaler: the engine's bf16/fp32 mix needs no loss scaling (precision.py).  The part of it that matters on long runs, skipping a
+step whose gradient is not finite, is `--skip-nonfinite-steps`: decided on the device inside the AdamW call, together with
+`--grad-clip-norm`.  In data-parallel runs the per-block gradient
 all-reduces launched during backward are awaited right before the optimizer step."""
 import logging
 import math
@@ -41,6 +43,14 @@ def student_teacher_ensemble(student, teacher, alpha=0.5):
     return {k: v * alpha + teacher[k] * (1.0 - alpha) for k, v in student.items()}
 
 
+def _grad_log(optimizer):
+    """' Grad norm: .. Clip: .. Skipped: N' when the optimizer ran guarded steps (a device read-back: log steps only)."""
+    stats = optimizer.grad_stats() if hasattr(optimizer, "grad_stats") else None
+    if stats is None:
+        return ""
+    return f" Grad norm: {stats['norm']:#.5g} Clip: {stats['clip_coef']:.4f} Skipped: {stats['skipped_total']}"
+
+
 def train_step(model, method, batch, optimizer, scheduler, step, dist_model, args, loss=None, next_batch=None):
     """One iteration of the loop body (train.py:80-119).  Returns (losses, batch_size, logit_scale).
     next_batch (optional): handed to method.prefetch_teacher() once this step's forward is queued, so the frozen teacher's pass
@@ -59,12 +69,21 @@ def train_step(model, method, batch, optimizer, scheduler, step, dist_model, arg
     backward(total_loss)
     if hasattr(model, "finish_grad_sync"):
         model.finish_grad_sync()
-    if getattr(args, "grad_clip_norm", None) is not None:
-        # data parallel: the buckets carry the SUM over ranks until AdamW divides by the world size, so the threshold is scaled
-        # with it -- the clip coefficient then equals the one of the mean gradient (= a single process on the union batch)
-        scale = float(getattr(model, "world", 1))
-        torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], args.grad_clip_norm * scale, norm_type=2.0)
-    optimizer.step()
+    clip, skip = getattr(args, "grad_clip_norm", None), bool(getattr(args, "skip_nonfinite_steps", False))
+    if (clip is not None or skip) and getattr(optimizer, "guard_available", lambda: False)():
+        # norm, clip coefficient and the non-finite-step skip inside cs_adamw_step: the norm is that of the reduced buffer times 1/world, i.e.
+        # of the mean gradient, identical bits on every rank -- the threshold is used as given and no rank decides differently.  p.grad is
+        # not rescaled.
+        optimizer.step(max_norm=clip, skip_nonfinite=skip)
+    elif skip:
+        optimizer.step(skip_nonfinite=True)              # raises: this backend cannot skip
+    else:
+        if clip is not None:
+            # data parallel: the buckets carry the SUM over ranks until AdamW divides by the world size, so the threshold is scaled
+            # with it -- the clip coefficient then equals the one of the mean gradient (= a single process on the union batch)
+            scale = float(getattr(model, "world", 1))
+            torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], clip * scale, norm_type=2.0)
+        optimizer.step()
     with torch.no_grad():
         # train.py:118-119 clamps every step.  A clamp of an unchanged, in-range scalar is the identity; skipping it then keeps the parameter's
         # version counter still, which RegionCLIP uses to read the temperature back from the device once instead of every step.
@@ -109,7 +128,7 @@ def train_one_epoch(model, method, data, loss, epoch, optimizer, scaler, schedul
                 f"Train Epoch: {epoch} [{num_samples:>{sample_digits}}/{dataloader.num_samples} "
                 f"({100.0 * batch_count / num_batches_per_epoch:.0f}%)] Data (t): {data_time_m.avg:.3f} "
                 f"Batch (t): {batch_time_m.avg:.3f}, {sps:#g}/s, {sps / args.world_size:#g}/s/gpu "
-                f"LR: {optimizer.param_groups[0]['lr']:5f} Logit Scale: {logit_scale.item():.3f} " + loss_log)
+                f"LR: {optimizer.param_groups[0]['lr']:5f} Logit Scale: {logit_scale.item():.3f} " + loss_log + _grad_log(optimizer))
             batch_time_m.reset()
             data_time_m.reset()
 

@@ -297,9 +297,35 @@ int cs_stream_create_cu_mask(int first_cu, int n_cus, cs_stream_t* out);
 int cs_stream_destroy(cs_stream_t stream);
 
 /* --- optimizer: torch.optim.AdamW built at src/training/main.py:198-213, stepped at src/training/train.py:115.
- * Flat fp32 master/grad/moment buffers; flags[n/64]: bit0 = tensor has a gradient this step, bit1 = weight decay applies. */
+ * Flat fp32 master/grad/moment buffers; flags[n/64]: bit0 = tensor has a gradient this step, bit1 = weight decay applies.
+ *
+ * guard == NULL: one launch; max_norm and skip_nonfinite are ignored.
+ *
+ * guard != NULL: gradient norm, clipping (torch.nn.utils.clip_grad_norm_, src/training/train.py:104-113) and the skip of a non-finite step
+ * (what GradScaler.step() does for the reference's `amp` precision, train.py:98-115) on the device, in three launches on `stream` and
+ * without atomics: the same inputs give the same bits.  guard is a device buffer of CS_ADAMW_GUARD_HEAD + ceil(n / CS_ADAMW_GUARD_SPAN)
+ * floats that the caller zeroes once:
+ *   guard[0]   overwritten: L2 norm of grad_scale * g over the ACTIVE granules (flag bit0); inactive granules are never loaded, so what
+ *              they hold -- NaN included -- does not matter.  Partial k sums elements [k * SPAN, (k + 1) * SPAN) in fp32 in a fixed order
+ *              that does not depend on the grid or the device, the partials are added in double: relative error of the norm < 1e-6.
+ *   guard[1]   overwritten: clip coefficient min(1, max_norm / (norm + 1e-6)) in fp32, clip_grad_norm_'s arithmetic (a NaN norm gives NaN, as
+ *              torch's clamp does); 1 when max_norm <= 0 = clipping off.  max_norm must not be NaN.
+ *   guard[2]   overwritten: 1.0 if the update was applied, 0.0 if it was skipped.
+ *   guard[3]   read-modify-write by one thread: number of skipped steps so far (+1 on a skip).
+ *   guard[4..7] never touched (reserved).
+ *   guard[8..] overwritten: the partial sums of squares.
+ * Skip: skip_nonfinite (0 or 1) != 0 and the norm is not finite (an Inf or NaN in an active granule, or a sum of squares beyond fp32) ->
+ * nothing is written to p, m, v and shadow.  With skip_nonfinite == 0 the arithmetic proceeds whatever the norm is, as clip_grad_norm_
+ * (error_if_nonfinite=False) followed by AdamW does.
+ * Scale: every gradient element is multiplied once by s = grad_scale * guard[1], formed once in fp32; with a coefficient of 1 every output
+ * is bit-identical to the guard == NULL call.
+ * `step` is the caller's 1-based count of ATTEMPTED steps: a skipped step still advances the bias-correction index, so that the host
+ * never reads the device back.  (GradScaler does not count skipped steps: after k skips the bias corrections here are those of step + k.) */
+#define CS_ADAMW_GUARD_HEAD 8
+#define CS_ADAMW_GUARD_SPAN 16384
 int cs_adamw_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, const uint8_t* flags, long n, float lr,
-                  float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, cs_stream_t stream);
+                  float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float max_norm,
+                  int skip_nonfinite, float* guard, cs_stream_t stream);
 
 #ifdef __cplusplus
 }
