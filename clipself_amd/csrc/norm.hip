@@ -174,8 +174,9 @@ __global__ __launch_bounds__(256) void ln_stats_finalize_kernel(const float* __r
         b += t;
     }
     const float mean = s / (float)C;
-    // pooled variance = within-slice part + between-slice part; only the latter (slice means against the row mean) can
-    // cancel, and it is a small share of the total unless the row mean dwarfs the row's spread
+    // pooled variance = within-slice part + between-slice part.  BOTH cancel when the row mean dwarfs the row's spread r = |mean| / sigma:
+    // the within-slice term sq.y - s_p^2 / n as badly as the between-slice term b - s * mean, so the relative error of rstd is about
+    // (P + 16) / 2 * 2^-24 * (1 + r^2) -- no better conditioned than a plain E[x^2] - mean^2, exact to 1e-4 up to r = 20 (profiles/ln_conditioning.md)
     const float m2 = q + fmaxf(b - s * mean, 0.f);
     mean_out[row] = mean;
     rstd_out[row] = rsqrtf(m2 / (float)C + eps);

@@ -108,7 +108,10 @@ class TowerEngine:
         # (rstd * (bf16(x) . W gamma - mean * colsum)): the bf16 rounding of x is relative to |x|, not to |x - mean|, so the error of the
         # normalised row grows like sqrt(1 + (mean / sigma)^2).  Measured against the plain schedule on weights with trained-like statistics
         # (oracle/stress_weights.py, profiles/r04_parity.md): outlier channels x200 alone -- folded is CLOSER to fp32 than the plain bf16
-        # schedule; |mean| / sigma = 2 -- equal; 3 -- 1.6x; 5 -- 2.8x.  So the first encode_image() after a weight load measures
+        # schedule; |mean| / sigma = 2 -- equal; 3 -- 1.6x; 5 -- 2.8x (whole tower: the frozen schedule's saved roundings elsewhere offset the
+        # fold's cost up to 2).  One LayerNorm -> GEMM alone, against fp64 (profiles/ln_conditioning.md, tests/test_gpu_ln_cond.py): folded /
+        # plain = 0.99 at 0, 1.13 at 1, 1.49 at 2, 1.91 at 3, 2.86 at 5 -- error^2 = floor^2 + b^2 (1 + r^2), the law diluted by the
+        # roundings both chains share; the limit of 2 thus caps a single fold at 1.5x.  So the first encode_image() after a weight load measures
         # mean_rows(|row mean| / row sigma) of the stream entering every block on a few crops (block_fold_statistic, one host read-back)
         # and keeps the block LayerNorms as LayerNorm kernels when it exceeds block_fold_limit.
         self.block_fold_guard = not trainable
