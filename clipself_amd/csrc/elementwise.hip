@@ -288,6 +288,67 @@ __global__ __launch_bounds__(256) void transpose_bf16_batched_kernel(const Trans
     transpose_tile(d.in, d.ld_in, d.out, d.ld_out, d.R, d.Cc, (local / d.tiles_x) * 64, (local % d.tiles_x) * 64, tile);
 }
 
+// Token taps of the frozen dense pass (cs_transpose_bf16 forms 1 / 2): out[b, c, p] = x[b * (HW + 1) + 1 + p, c] -- the fp32 residual
+// stream after a block, token-major with the CLS row first, copied out as the [B, C, h, w] map a convolutional neck reads (F-ViT
+// evaclip_vit.py:117-122 `_expand_x`), fp32 or rounded to bf16 (RNE).  One 64-token x 64-channel tile per workgroup through LDS, rows
+// padded to 65 dwords.  Dword LDS accesses are banked modulo 32 within each 32-lane half of a wave, so the vector paths give a half-wave
+// one 32-dword half of the tile's width: staging, 4 token rows x 8 float4 -- the dword of lane (r, cv) goes to bank (r + cv + e) mod 32,
+// cv in {0, 4 .. 28}, 32 distinct; transposed reads, 4 channels x 8 token groups of 4 (fp32 out) or 8 channels x 4 groups of 8 (bf16 out)
+// -- bank (pv + e + c) mod 32, again 32 distinct.  Global reads are 128 contiguous bytes per token row and half-wave, writes 128 (fp32)
+// or 64 (bf16) per channel row; the other half of a row follows in a later pass of the same workgroup.  Each side takes 16-byte
+// accesses when its alignment and a full tile allow, else one element per lane (rows of 65 dwords: conflict-free as well).
+template <typename TO>
+__global__ __launch_bounds__(256) void tokens_to_nchw_kernel(const float* __restrict__ x, long ldx, TO* __restrict__ out, int HW, int C) {
+    __shared__ float tile[64][65];
+    constexpr int VO = sizeof(TO) == 4 ? 4 : 8;                         // tokens per 16-byte store
+    const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z;
+    const float* src = x + ((size_t)b * (HW + 1) + 1) * ldx;            // the image's first patch row
+    TO* dst = out + (size_t)b * C * HW;
+    const bool vec_in = (ldx & 3) == 0 && ((uintptr_t)x & 15) == 0 && c0 + 64 <= C;
+    const bool vec_out = (HW % VO) == 0 && ((uintptr_t)out & 15) == 0 && p0 + 64 <= HW;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    if (vec_in) {
+#pragma unroll
+        for (int pss = 0; pss < 4; ++pss) {
+            const int v = threadIdx.x + pss * 256, r = (v >> 3) & 63, cv = (v >> 9) * 32 + (v & 7) * 4;      // 64 token rows x 8 vectors x 2 halves
+            if (p0 + r < HW) {
+                const float4 t = *(const float4*)(src + (size_t)(p0 + r) * ldx + c0 + cv);
+                tile[r][cv] = t.x; tile[r][cv + 1] = t.y; tile[r][cv + 2] = t.z; tile[r][cv + 3] = t.w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int r = ty * 16 + i;
+            if (p0 + r < HW && c0 + tx < C) tile[r][tx] = src[(size_t)(p0 + r) * ldx + c0 + tx];
+        }
+    }
+    __syncthreads();
+    if (vec_out) {
+        constexpr int VPH = 32 / VO;                                                    // 16-byte vectors per 32-token half of a channel row
+#pragma unroll
+        for (int pss = 0; pss < 16 / VO; ++pss) {                                       // 64 channel rows x VPH vectors x 2 halves: 4 passes (fp32), 2 (bf16)
+            const int v = threadIdx.x + pss * 256, c = (v / VPH) & 63, pv = (v / (VPH * 64)) * 32 + (v % VPH) * VO;
+            if (c0 + c >= C) continue;
+            TO* o = dst + (size_t)(c0 + c) * HW + p0 + pv;
+            if constexpr (VO == 4) {
+                *(float4*)o = make_float4(tile[pv][c], tile[pv + 1][c], tile[pv + 2][c], tile[pv + 3][c]);
+            } else {
+                U128 w;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) w.e[e] = f2bf(tile[pv + e][c]);
+                *(uint4*)o = w.u;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = ty * 16 + i;
+            if (c0 + c < C && p0 + tx < HW) dst[(size_t)(c0 + c) * HW + p0 + tx] = (TO)tile[tx][c];
+        }
+    }
+}
+
 // out[n] += sum_m x[m, n]   (bias gradients; bf16 in, f32 out).  grid.x tiles columns, grid.y splits rows into blocks whose partial sums
 // go to a workspace row each; colsum_reduce_kernel adds them up in a fixed order.
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const __bf16* __restrict__ x, long ldx, float* __restrict__ out, int M, int N,
@@ -480,10 +541,23 @@ extern "C" int cs_cast_f32_bf16(const float* x, void* y, long n, hipStream_t str
     CS_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, hipStream_t stream) {
-    CS_CHECK_ARG(R > 0 && Cc > 0 && ld_out >= R, "cs_transpose_bf16: bad shape R=%d C=%d ld_out=%ld", R, Cc, ld_out);
-    dim3 grid((Cc + 63) / 64, (int)((ld_out + 63) / 64));
-    hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0, stream, (const __bf16*)in, ld_in, (__bf16*)out, ld_out, R, Cc);
+// form 0: the padded bf16 transpose above (batch must be 1).  form 1 / 2: the token taps of a frozen dense pass -- in = the fp32 residual
+// stream x[batch * (R + 1), ld_in] (R = h * w patch tokens per image behind its CLS row, Cc = C channels, ld_in >= C), out = [batch, Cc, R]
+// contiguous (ld_out == R), fp32 (1) or bf16 (2): out[b, c, p] = x[b * (R + 1) + 1 + p, c]  (tokens_to_nchw_kernel).
+extern "C" int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, hipStream_t stream) {
+    if (form == 0) {
+        CS_CHECK_ARG(R > 0 && Cc > 0 && ld_out >= R && batch == 1, "cs_transpose_bf16: bad shape R=%d C=%d ld_out=%ld batch=%d", R, Cc, ld_out, batch);
+        dim3 grid((Cc + 63) / 64, (int)((ld_out + 63) / 64));
+        hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0, stream, (const __bf16*)in, ld_in, (__bf16*)out, ld_out, R, Cc);
+        CS_LAUNCH_CHECK();
+        return 0;
+    }
+    CS_CHECK_ARG(form == 1 || form == 2, "cs_transpose_bf16: form %d (0 bf16 transpose, 1 / 2 token taps to fp32 / bf16)", form);
+    CS_CHECK_ARG(in && out && R > 0 && Cc > 0 && batch > 0 && batch <= 65535 && ld_in >= Cc && ld_out == R && (Cc + 63) / 64 <= 65535,
+                 "cs_transpose_bf16 (token taps): batch=%d (1..65535) tokens=%d C=%d ld_in=%ld (>= C) ld_out=%ld (== tokens)", batch, R, Cc, ld_in, ld_out);
+    const dim3 grid((R + 63) / 64, (Cc + 63) / 64, batch);
+    if (form == 1) hipLaunchKernelGGL(tokens_to_nchw_kernel<float>, grid, dim3(256), 0, stream, (const float*)in, ld_in, (float*)out, R, Cc);
+    else hipLaunchKernelGGL(tokens_to_nchw_kernel<__bf16>, grid, dim3(256), 0, stream, (const float*)in, ld_in, (__bf16*)out, R, Cc);
     CS_LAUNCH_CHECK();
     return 0;
 }

@@ -434,10 +434,34 @@ class TowerEngine:
         return out
 
     # ------------------------------------------------------------------------------------------ student
-    def encode_dense(self, images, need_grad: bool = False):
+    def _check_taps(self, taps, need_grad):
+        """taps of encode_dense: a sorted tuple of distinct block indices in [0, L-1], on a frozen pass, on a backend that can copy them out."""
+        L = self.cfg.layers
+        taps = tuple(int(i) for i in taps)
+        if need_grad:
+            raise ValueError("encode_dense(taps=...) is the frozen detector-backbone pass: it cannot keep activations (need_grad=True)")
+        if any(not 0 <= i < L for i in taps):
+            raise ValueError(f"encode_dense(taps={taps}): block indices must lie in [0, {L - 1}] for this {L}-block tower")
+        if any(b <= a for a, b in zip(taps, taps[1:])):
+            raise ValueError(f"encode_dense(taps={taps}): block indices must be strictly ascending (the order the blocks run in)")
+        if not getattr(self.ops, "TOKEN_TAPS", False):
+            raise NotImplementedError(f"block taps (encode_dense(taps=...), forward_intermediates, the detector backbone) need the "
+                                      f"tokens-to-[B, C, h, w] copy of the residual stream, which the kernel backend "
+                                      f"{getattr(self.ops, 'name', type(self.ops).__name__)!r} does not provide (no TOKEN_TAPS)")
+        return taps
+
+    def encode_dense(self, images, need_grad: bool = False, taps=None, final: bool = True, tap_dtype=F32):
         """Dense path -> L2-normalised token map fp32 [B, N, E] (row 0 of each image is the unused CLS slot).
-        With need_grad the activations of the trainable blocks (and of a trainable stem) are kept for backward_dense()."""
+        With need_grad the activations of the trainable blocks (and of a trainable stem) are kept for backward_dense().
+        taps (frozen pass only): block indices whose output -- the in-place residual stream after that block, index L-1 being the output of
+        the last block's attention-free form -- is copied out as a [B, C, h, w] map (tap_dtype fp32 or bf16) before the next block
+        overwrites it (F-ViT evaclip_vit.py:90-97); the method then returns (map, grid, [tap maps]).  final=False stops after the last
+        block: no final LayerNorm, head or normalisation, None for the map (the backbone's training-mode branch, :98-106)."""
         ops, cfg, fn = self.ops, self.cfg, self.prefix + self.FINAL_NORM
+        if taps is not None:
+            taps = self._check_taps(taps, need_grad)
+        if need_grad and not final:
+            raise ValueError("encode_dense(need_grad=True) differentiates the normalised map: final=False leaves nothing to differentiate")
         B = images.shape[0]
         stem_keep = {} if (need_grad and self._pos_trains()) else None
         x, g = self._stem(images, stem_keep)
@@ -445,12 +469,18 @@ class TowerEngine:
         cos, sin = self.rope_tables(g)
         xf = x.view(B * N, C)
         saves = {}
+        maps = []
         for i in range(cfg.layers):
             keep = need_grad and i >= self.first_trainable
             save = {} if keep else None
             xf = self._block_fwd(i, xf, B, N, cos, sin, with_attn=(i < cfg.layers - 1), save=save, inplace=not keep)
             if keep:
                 saves[i] = save
+            if taps is not None and i in taps:
+                maps.append(ops.empty((B, C, g, g), tap_dtype))
+                ops.tokens_to_nchw(xf, B, N, C, maps[-1])
+        if not final:
+            return (None, g) if taps is None else (None, g, maps)
         M = B * N
         lnf = ops.empty((M, C), BF16)
         mean = ops.empty((M,), F32) if need_grad else None
@@ -464,7 +494,7 @@ class TowerEngine:
         if need_grad:
             self._ctx = dict(B=B, N=N, g=g, saves=saves, xL=xf, stf=(mean, rstd), dense=dense, inv=inv, cos=cos, sin=sin, stem=stem_keep,
                              lnf=lnf if self.train_all else None)
-        return dense.view(B, N, E), g
+        return (dense.view(B, N, E), g) if taps is None else (dense.view(B, N, E), g, maps)
 
     def roi_pool(self, dense, rois, g):
         """rois [K,5] = (image index, x0,y0,x1,y1 normalised to [0,1]) -> fp32 [K,E]."""

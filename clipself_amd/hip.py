@@ -60,7 +60,7 @@ SIGNATURES = {
     "cs_gelu_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp]),
     "cs_gelu_bwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp]),
     "cs_cast_f32_bf16": (_i, [_vp, _vp, _l, _vp]),
-    "cs_transpose_bf16": (_i, [_vp, _l, _vp, _l, _i, _i, _vp]),
+    "cs_transpose_bf16": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp]),
     "cs_transpose_bf16_batched": (_i, [_vp, _i, _i, _vp]),
     "cs_colsum_workspace": (_sz, [_i, _i]),
     "cs_colsum_bf16": (_i, [_vp, _l, _vp, _vp, _i, _i, _vp]),
@@ -141,6 +141,7 @@ class HipOps:
     ATTN_CAUSAL = True                  # attn_query_fwd(allow=None): causal self-attention, what the text tower (encode_text) runs on
     ADAMW_GUARD = True                  # adamw_step(max_norm=, skip_nonfinite=, guard=): gradient norm, clipping and the non-finite-step skip on the device
     ATTN_NO_ROPE = True                 # attn_fwd / attn_fwd_stats / attn_cls_fwd / attn_bwd(cos=None, sin=None): no rotary embedding, any Ntok > 1
+    TOKEN_TAPS = True                   # tokens_to_nchw: the residual stream after a block as a [B, C, h, w] map (encode_dense(taps=), the detector backbone)
 
     def __init__(self):
         self.lib = load_library()
@@ -590,7 +591,15 @@ class HipOps:
         self._chk(inp, out)
         R, Cc = inp.shape
         assert out.shape[0] == Cc and out.is_contiguous()
-        self._ok(self.lib.cs_transpose_bf16(_p(inp), inp.stride(0), _p(out), out.shape[1], R, Cc, self._stream()), "cs_transpose_bf16")
+        self._ok(self.lib.cs_transpose_bf16(_p(inp), inp.stride(0), _p(out), out.shape[1], R, Cc, 0, 1, self._stream()), "cs_transpose_bf16")
+
+    def tokens_to_nchw(self, x, B, N, C, out):
+        """x fp32 [B*N, >= C] (row stride ldx), token-major, each image's CLS row first -> out [B, C, h, w] contiguous, fp32 or bf16 (RNE):
+        out[b, c, p] = x[b*N + 1 + p, c] -- forms 1 / 2 of cs_transpose_bf16 (evaclip_vit.py:117-122 `_expand_x`)."""
+        self._chk(x, out)
+        assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == B * N and x.shape[1] >= C and N >= 2
+        assert out.is_contiguous() and out.dim() == 4 and out.shape[0] == B and out.shape[1] == C and out.shape[2] * out.shape[3] == N - 1
+        self._ok(self.lib.cs_transpose_bf16(_p(x), x.stride(0), _p(out), N - 1, N - 1, C, 1 + _dt(out), B, self._stream()), "cs_transpose_bf16")
 
     def transpose_bf16_batched(self, pairs):
         """[(inp [R, C], out [C, ld_out >= R]), ...] -> every out = inp^T (zero padded) in ONE launch.  The device descriptor table is

@@ -8,6 +8,8 @@ src/open_clip/eva_clip/eva_vit_model.py:396-711 `EVAVisionTransformer`):
   model.encode_pseudo_boxes(x, list[Tensor[k_i,4]], normalize=False, extract_type='v2') -> [K, E]
   model.encode_masks(x, masks, normalize=True)                         -> [sum masks, E]
   model.encode_text(ids, normalize=False)                              -> [B, E]   (frozen text tower, engine_text.py; token ids in)
+  model.visual.forward_intermediates(x, out_indices, final_map=True)   -> ([B, width, h, w] per index, [B, E, h, w] | None): the detector
+                                                                          backbone's pass (clipself_amd/fvit.py, F-ViT evaclip_vit.py:61-106)
   model.lock_image_tower(unlocked_groups, freeze_bn_stats), .set_grad_checkpointing(), .logit_scale,
   model.visual.image_size / image_mean / image_std, .train() / .eval(), .state_dict() with the reference's keys.
 
@@ -203,6 +205,17 @@ class EVAVisionTower(_Node):
         if keep_shape:
             return feats.reshape(x.shape[0], g, g, -1).permute(0, 3, 1, 2)
         return feats
+
+    def forward_intermediates(self, x, out_indices, final_map: bool = True, dtype=torch.float32):
+        """One frozen pass for a detector backbone (F-ViT/models/evaclip_vit.py:61-106): the residual stream after the blocks `out_indices`
+        (ascending; layers - 1 = the output of the last block's attention-free form) as [B, width, h, w] maps of `dtype` (fp32 or bf16), and
+        the L2-normalised dense map as [B, E, h, w] -- the values of encode_dense(keep_shape=True) -- or None with final_map=False, which
+        also skips the final norm and the head.  Runs under no_grad whatever the tower's training state; outputs are detached."""
+        with torch.no_grad():
+            x = x.to(self.engine.device)
+            dense, g, maps = self.engine.encode_dense(x, need_grad=False, taps=tuple(out_indices), final=final_map, tap_dtype=dtype)
+            fmap = dense[:, 1:].reshape(x.shape[0], g, g, -1).permute(0, 3, 1, 2) if final_map else None
+        return maps, fmap
 
     def extract_roi_features(self, x, normed_boxes, **kwargs):
         dense, g = self._dense(x)

@@ -232,7 +232,14 @@ int cs_gelu_bwd(const void* dy, long lddy, const void* x, long ldx, void* dx, lo
 
 /* --- data movement helpers of the step */
 int cs_cast_f32_bf16(const float* x, void* y, long n, cs_stream_t stream);
-int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, cs_stream_t stream); /* out[c,r]; zero pad r in [R, ld_out) */
+/* form 0 (batch == 1): bf16 in [R, Cc] -> bf16 out[c, r], zero pad r in [R, ld_out).
+ * form 1 / 2, the token taps of a detector backbone (F-ViT/models/evaclip_vit.py:117-122 `_expand_x`: x[:, 1:].permute(0, 2, 1).contiguous()
+ * .view(-1, width, h, w) of the residual stream after a block): in = fp32 x[batch * (R + 1), ld_in], token-major rows of `batch` images,
+ * each with its CLS row first and R = h * w patch rows behind it; out = [batch, Cc, R] contiguous (ld_out == R), fp32 (form 1) or bf16
+ * (form 2, round to nearest even): out[b, c, p] = x[b * (R + 1) + 1 + p, c].  Any R >= 1, Cc >= 1, ld_in >= Cc; the CLS rows and the
+ * columns [Cc, ld_in) are never read.  16-byte accesses where ld_in % 4 == 0 / R % 4 (fp32) or R % 8 (bf16) == 0 and the pointers are
+ * 16-byte aligned, one element per lane otherwise.  Plain loads and stores, no workspace. */
+int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, cs_stream_t stream);
 /* `count` such transposes in one launch (the W^T shadows the dgrad GEMMs read are rebuilt after every AdamW step: eva_vit_model.py:99-103,
  * 177-179,218-219 are the linears; 49 matrices per step for B/16).  desc = DEVICE array of 48-byte records
  *   { const void* in; void* out; long ld_in; long ld_out; int R; int Cc; int tile0; int tiles_x; }
