@@ -349,6 +349,163 @@ __global__ __launch_bounds__(256) void tokens_to_nchw_kernel(const float* __rest
     }
 }
 
+// The detector neck's 2 x 2 transposed convolutions as GEMMs on token rows (cs_transpose_bf16 forms 4 / 5).  With s the
+// upsampling factor (1 or 2), off the CLS rows in front of each image's P = h * w rows and column block q = di * s + dj:
+//     nchw[b, c, s*i + di, s*j + dj]  <->  rows[b * (P + off) + off + i*w + j, q * C + c]
+// For a fixed (b, di) the elements of one channel are numbered u = s * (i*w + j) + dj in [0, s*P): u runs along the output's memory
+// except for a jump at every grid row, nchw offset = c * s*s*P + u + s*w * ((s - 1) * i + di), and along the rows tensor it alternates
+// the s column blocks of one token.  So both kernels are the 64 x 64 transposes of tokens_to_nchw_kernel with u in the place of the
+// token: grid (u tile, channel tile, b * s + di), fp32 tile in LDS with rows of 65 dwords, and the same half-wave layouts -- on the
+// u-contiguous side 4 (fp32) or 8 (bf16) elements per 16-byte access, bank (uv + e + c) mod 32; on the channel-contiguous side 4 rows x 8
+// float4 or 8 rows x 4 vectors of 8 bf16 per 32-dword half of the tile's width, bank (r + cv + e) mod 32: 32 distinct in each case.  A
+// 16-byte access on the u side needs s*w to be a multiple of its element count (then no vector straddles a grid row and every vector is
+// aligned), on the channel side C and the row stride to be; pointers 16-byte aligned and a full tile on that side, else one element per
+// lane with bounds checks.  bf16 -> fp32 is exact, fp32 -> bf16 rounds to nearest even once, at the store.  Indices are 64-bit.
+struct DeconvGeom {
+    int P, w, C, s, off;      // tokens per image, grid width, channels, upsampling factor, CLS rows per image
+};
+__device__ __forceinline__ size_t deconv_nchw_offset(const DeconvGeom& g, int c, int u, int di) {
+    const int i = (u >> (g.s - 1)) / g.w;
+    return (size_t)c * ((size_t)g.s * g.s * g.P) + (size_t)u + (size_t)g.s * g.w * (size_t)((g.s - 1) * i + di);
+}
+__device__ __forceinline__ size_t deconv_rows_offset(const DeconvGeom& g, long ld, int b, int u, int di) {      // of channel 0
+    return ((size_t)b * (g.P + g.off) + g.off + (u >> (g.s - 1))) * (size_t)ld + (size_t)(di * g.s + (u & (g.s - 1))) * g.C;
+}
+__device__ __forceinline__ float deconv_ld(const float* p) { return *p; }
+__device__ __forceinline__ float deconv_ld(const __bf16* p) { return bf2f(*p); }
+__device__ __forceinline__ void deconv_st(float* p, float v) { *p = v; }
+__device__ __forceinline__ void deconv_st(__bf16* p, float v) { *p = f2bf(v); }
+
+// 64 u rows x 64 channels between the rows tensor and the tile: tile[u - u0][c - c0]
+template <typename T>
+__device__ __forceinline__ void deconv_rows_load(const T* __restrict__ rows, long ld, const DeconvGeom& g, int b, int di, int u0, int c0,
+                                                 int U, bool vec, float (*tile)[65]) {
+    constexpr int V = 16 / sizeof(T), LOG = sizeof(T) == 4 ? 3 : 2;        // elements per vector, log2(vectors per 32-channel half)
+    if (vec) {
+#pragma unroll
+        for (int pss = 0; pss < 16 / V; ++pss) {
+            const int v = threadIdx.x + pss * 256, r = (v >> LOG) & 63, cv = (v >> (LOG + 6)) * 32 + (v & ((1 << LOG) - 1)) * V;
+            if (u0 + r < U) {
+                const T* p = rows + deconv_rows_offset(g, ld, b, u0 + r, di) + c0 + cv;
+                if constexpr (V == 4) {
+                    const float4 t = *(const float4*)p;
+                    tile[r][cv] = t.x; tile[r][cv + 1] = t.y; tile[r][cv + 2] = t.z; tile[r][cv + 3] = t.w;
+                } else {
+                    U128 t;
+                    t.u = *(const uint4*)p;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) tile[r][cv + e] = bf2f(t.e[e]);
+                }
+            }
+        }
+        return;
+    }
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int r = ty * 16 + i;
+        if (u0 + r < U && c0 + tx < g.C) tile[r][tx] = deconv_ld(rows + deconv_rows_offset(g, ld, b, u0 + r, di) + c0 + tx);
+    }
+}
+// ... and between the tile and the NCHW tensor: the image's channel rows, V consecutive u per vector
+template <typename T, bool STORE>
+__device__ __forceinline__ void deconv_nchw_move(T* __restrict__ img, const DeconvGeom& g, int di, int u0, int c0, int U, bool vec,
+                                                 float (*tile)[65]) {
+    constexpr int V = 16 / sizeof(T), VPH = 32 / V;                         // 16-byte vectors per 32-u half of a channel row
+    if (vec) {
+#pragma unroll
+        for (int pss = 0; pss < 16 / V; ++pss) {                             // 64 channel rows x VPH vectors x 2 halves
+            const int v = threadIdx.x + pss * 256, c = (v / VPH) & 63, uv = (v / (VPH * 64)) * 32 + (v % VPH) * V;
+            if (c0 + c >= g.C) continue;
+            T* p = img + deconv_nchw_offset(g, c0 + c, u0 + uv, di);
+            if constexpr (STORE) {
+                if constexpr (V == 4) {
+                    *(float4*)p = make_float4(tile[uv][c], tile[uv + 1][c], tile[uv + 2][c], tile[uv + 3][c]);
+                } else {
+                    U128 t;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) t.e[e] = f2bf(tile[uv + e][c]);
+                    *(uint4*)p = t.u;
+                }
+            } else {
+                if constexpr (V == 4) {
+                    const float4 t = *(const float4*)p;
+                    tile[uv][c] = t.x; tile[uv + 1][c] = t.y; tile[uv + 2][c] = t.z; tile[uv + 3][c] = t.w;
+                } else {
+                    U128 t;
+                    t.u = *(const uint4*)p;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) tile[uv + e][c] = bf2f(t.e[e]);
+                }
+            }
+        }
+        return;
+    }
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int c = ty * 16 + i;
+        if (c0 + c < g.C && u0 + tx < U) {
+            T* p = img + deconv_nchw_offset(g, c0 + c, u0 + tx, di);
+            if constexpr (STORE) deconv_st(p, tile[tx][c]);
+            else tile[tx][c] = deconv_ld(p);
+        }
+    }
+}
+template <typename T>
+__device__ __forceinline__ bool deconv_vec_rows(const T* rows, long ld, const DeconvGeom& g, int c0) {
+    constexpr int V = 16 / sizeof(T);
+    return (ld % V) == 0 && (g.C % V) == 0 && ((uintptr_t)rows & 15) == 0 && c0 + 64 <= g.C;
+}
+template <typename T>
+__device__ __forceinline__ bool deconv_vec_nchw(const T* img, const DeconvGeom& g, int u0, int U) {
+    constexpr int V = 16 / sizeof(T);
+    return ((g.s * g.w) % V) == 0 && ((uintptr_t)img & 15) == 0 && u0 + 64 <= U;
+}
+
+// form 4: out[b, c, s*i + di, s*j + dj] = rows[b * (P + off) + off + i*w + j, (di*s + dj) * C + c]
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void rows_to_nchw_kernel(const TI* __restrict__ rows, long ld, TO* __restrict__ out, DeconvGeom g) {
+    __shared__ float tile[64][65];
+    const int u0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z >> (g.s - 1), di = blockIdx.z & (g.s - 1), U = g.s * g.P;
+    TO* img = out + (size_t)b * g.C * ((size_t)g.s * g.s * g.P);
+    deconv_rows_load(rows, ld, g, b, di, u0, c0, U, deconv_vec_rows(rows, ld, g, c0), tile);
+    __syncthreads();
+    deconv_nchw_move<TO, true>(img, g, di, u0, c0, U, deconv_vec_nchw(out, g, u0, U), tile);
+}
+
+// form 5, the inverse, bf16 rows out; with off = 1 the image's CLS row gets s*s*C zeros (the u tile 0 of each (b, di, channel tile) writes
+// the s column blocks of its di)
+template <typename TI>
+__global__ __launch_bounds__(256) void nchw_to_rows_kernel(const TI* __restrict__ in, __bf16* __restrict__ rows, long ld, DeconvGeom g) {
+    __shared__ float tile[64][65];
+    const int u0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z >> (g.s - 1), di = blockIdx.z & (g.s - 1), U = g.s * g.P;
+    const TI* img = in + (size_t)b * g.C * ((size_t)g.s * g.s * g.P);
+    deconv_nchw_move<const TI, false>(img, g, di, u0, c0, U, deconv_vec_nchw(in, g, u0, U), tile);
+    __syncthreads();
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    if (g.off && u0 == 0 && ty < g.s && c0 + tx < g.C)
+        rows[(size_t)b * (g.P + g.off) * (size_t)ld + (size_t)(di * g.s + ty) * g.C + c0 + tx] = f2bf(0.f);
+    if (deconv_vec_rows(rows, ld, g, c0)) {
+#pragma unroll
+        for (int pss = 0; pss < 2; ++pss) {                                  // 64 u rows x 4 vectors of 8 channels x 2 halves
+            const int v = threadIdx.x + pss * 256, r = (v >> 2) & 63, cv = (v >> 8) * 32 + (v & 3) * 8;
+            if (u0 + r < U) {
+                U128 t;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) t.e[e] = f2bf(tile[r][cv + e]);
+                *(uint4*)(rows + deconv_rows_offset(g, ld, b, u0 + r, di) + c0 + cv) = t.u;
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int r = ty * 16 + i;
+        if (u0 + r < U && c0 + tx < g.C) rows[deconv_rows_offset(g, ld, b, u0 + r, di) + c0 + tx] = f2bf(tile[r][tx]);
+    }
+}
+
 // out[n] += sum_m x[m, n]   (bias gradients; bf16 in, f32 out).  grid.x tiles columns, grid.y splits rows into blocks whose partial sums
 // go to a workspace row each; colsum_reduce_kernel adds them up in a fixed order.
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const __bf16* __restrict__ x, long ldx, float* __restrict__ out, int M, int N,
@@ -541,7 +698,35 @@ extern "C" int cs_cast_f32_bf16(const float* x, void* y, long n, hipStream_t str
     CS_LAUNCH_CHECK();
     return 0;
 }
-// form 0: the padded bf16 transpose above (batch must be 1).  form 1 / 2: the token taps of a frozen dense pass -- in = the fp32 residual
+// Forms 4 / 5 of cs_transpose_bf16 (low byte of `form`): rows -> NCHW and NCHW -> rows of the 2x2 deconvolution GEMMs.  form bit 8 = s - 1,
+// bit 9 = off, bit 10 / 11 = element type of the rows / of the NCHW tensor (0 fp32, 1 bf16), bits 12-31 = grid width w; R = h * w,
+// Cc = C, batch = B; the rows tensor's stride is ld_in (form 4) / ld_out (form 5) >= s*s*C, the NCHW tensor is contiguous and its ld is
+// ignored.  Form 5 writes bf16 rows only.
+static int deconv_rows_launch(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, hipStream_t stream) {
+    const bool to_rows = (form & 255) == 5;
+    const int s = 1 + ((form >> 8) & 1), off = (form >> 9) & 1, rows_bf16 = (form >> 10) & 1, nchw_bf16 = (form >> 11) & 1;
+    const int w = (int)((unsigned)form >> 12);
+    const long ld = to_rows ? ld_out : ld_in;
+    CS_CHECK_ARG(in && out && R > 0 && R <= (1 << 29) && Cc > 0 && w > 0 && R % w == 0 && batch > 0 && batch * s <= 65535 && (Cc + 63) / 64 <= 65535 &&
+                     ld >= (long)s * s * Cc && (!to_rows || rows_bf16),
+                 "cs_transpose_bf16 (rows <-> NCHW, form %d): batch=%d (batch * s <= 65535) tokens=%d (a multiple of w=%d) C=%d s=%d rows stride=%ld "
+                 "(>= s*s*C)%s", form & 255, batch, R, w, Cc, s, ld, to_rows && !rows_bf16 ? "; NCHW -> rows writes bf16 rows (form bit 10)" : "");
+    const DeconvGeom g{R, w, Cc, s, off};
+    const dim3 grid((unsigned)(((long)s * R + 63) / 64), (Cc + 63) / 64, batch * s), block(256);
+    if (to_rows) {
+        if (nchw_bf16) hipLaunchKernelGGL(nchw_to_rows_kernel<__bf16>, grid, block, 0, stream, (const __bf16*)in, (__bf16*)out, ld, g);
+        else hipLaunchKernelGGL(nchw_to_rows_kernel<float>, grid, block, 0, stream, (const float*)in, (__bf16*)out, ld, g);
+    } else if (rows_bf16) {
+        if (nchw_bf16) hipLaunchKernelGGL((rows_to_nchw_kernel<__bf16, __bf16>), grid, block, 0, stream, (const __bf16*)in, ld, (__bf16*)out, g);
+        else hipLaunchKernelGGL((rows_to_nchw_kernel<__bf16, float>), grid, block, 0, stream, (const __bf16*)in, ld, (float*)out, g);
+    } else {
+        if (nchw_bf16) hipLaunchKernelGGL((rows_to_nchw_kernel<float, __bf16>), grid, block, 0, stream, (const float*)in, ld, (__bf16*)out, g);
+        else hipLaunchKernelGGL((rows_to_nchw_kernel<float, float>), grid, block, 0, stream, (const float*)in, ld, (float*)out, g);
+    }
+    CS_LAUNCH_CHECK();
+    return 0;
+}
+// form 0: the padded bf16 transpose above (batch must be 1).  forms 4 / 5 (low byte): deconv_rows_launch above.  form 1 / 2: the token taps of a frozen dense pass -- in = the fp32 residual
 // stream x[batch * (R + 1), ld_in] (R = h * w patch tokens per image behind its CLS row, Cc = C channels, ld_in >= C), out = [batch, Cc, R]
 // contiguous (ld_out == R), fp32 (1) or bf16 (2): out[b, c, p] = x[b * (R + 1) + 1 + p, c]  (tokens_to_nchw_kernel).
 extern "C" int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, hipStream_t stream) {
@@ -552,7 +737,9 @@ extern "C" int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_
         CS_LAUNCH_CHECK();
         return 0;
     }
-    CS_CHECK_ARG(form == 1 || form == 2, "cs_transpose_bf16: form %d (0 bf16 transpose, 1 / 2 token taps to fp32 / bf16)", form);
+    if ((form & 255) == 4 || (form & 255) == 5) return deconv_rows_launch(in, ld_in, out, ld_out, R, Cc, form, batch, stream);
+    CS_CHECK_ARG(form == 1 || form == 2,
+                 "cs_transpose_bf16: form %d (0 bf16 transpose, 1 / 2 token taps to fp32 / bf16, low byte 4 / 5 rows <-> NCHW of the 2x2 deconvolution)", form);
     CS_CHECK_ARG(in && out && R > 0 && Cc > 0 && batch > 0 && batch <= 65535 && ld_in >= Cc && ld_out == R && (Cc + 63) / 64 <= 65535,
                  "cs_transpose_bf16 (token taps): batch=%d (1..65535) tokens=%d C=%d ld_in=%ld (>= C) ld_out=%ld (== tokens)", batch, R, Cc, ld_in, ld_out);
     const dim3 grid((R + 63) / 64, (Cc + 63) / 64, batch);

@@ -450,16 +450,21 @@ class TowerEngine:
                                       f"{getattr(self.ops, 'name', type(self.ops).__name__)!r} does not provide (no TOKEN_TAPS)")
         return taps
 
-    def encode_dense(self, images, need_grad: bool = False, taps=None, final: bool = True, tap_dtype=F32):
+    def encode_dense(self, images, need_grad: bool = False, taps=None, final: bool = True, tap_dtype=F32, tap_rows=()):
         """Dense path -> L2-normalised token map fp32 [B, N, E] (row 0 of each image is the unused CLS slot).
         With need_grad the activations of the trainable blocks (and of a trainable stem) are kept for backward_dense().
         taps (frozen pass only): block indices whose output -- the in-place residual stream after that block, index L-1 being the output of
         the last block's attention-free form -- is copied out as a [B, C, h, w] map (tap_dtype fp32 or bf16) before the next block
         overwrites it (F-ViT evaclip_vit.py:90-97); the method then returns (map, grid, [tap maps]).  final=False stops after the last
-        block: no final LayerNorm, head or normalisation, None for the map (the backbone's training-mode branch, :98-106)."""
+        block: no final LayerNorm, head or normalisation, None for the map (the backbone's training-mode branch, :98-106).
+        tap_rows: positions within `taps` whose tap is delivered as neck.TokenRows instead of a map -- the whole stream [B*N, C], CLS
+        rows included (off = 1), cast to bf16 by one cs_cast_f32_bf16 launch: the operand a Deconv2x2 contracts as it is."""
         ops, cfg, fn = self.ops, self.cfg, self.prefix + self.FINAL_NORM
         if taps is not None:
             taps = self._check_taps(taps, need_grad)
+        tap_rows = tuple(int(k) for k in tap_rows)
+        if tap_rows and (taps is None or any(not 0 <= k < len(taps) for k in tap_rows)):
+            raise ValueError(f"encode_dense(tap_rows={tap_rows}): positions within taps={taps}")
         if need_grad and not final:
             raise ValueError("encode_dense(need_grad=True) differentiates the normalised map: final=False leaves nothing to differentiate")
         B = images.shape[0]
@@ -477,8 +482,15 @@ class TowerEngine:
             if keep:
                 saves[i] = save
             if taps is not None and i in taps:
-                maps.append(ops.empty((B, C, g, g), tap_dtype))
-                ops.tokens_to_nchw(xf, B, N, C, maps[-1])
+                if len(maps) in tap_rows:
+                    from .neck import TokenRows
+                    assert xf.is_contiguous()
+                    rows = ops.empty((B * N, C), BF16)
+                    ops.cast_f32_bf16(xf, rows)
+                    maps.append(TokenRows(rows, B, g, g, 1))
+                else:
+                    maps.append(ops.empty((B, C, g, g), tap_dtype))
+                    ops.tokens_to_nchw(xf, B, N, C, maps[-1])
         if not final:
             return (None, g) if taps is None else (None, g, maps)
         M = B * N

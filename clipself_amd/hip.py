@@ -142,6 +142,7 @@ class HipOps:
     ADAMW_GUARD = True                  # adamw_step(max_norm=, skip_nonfinite=, guard=): gradient norm, clipping and the non-finite-step skip on the device
     ATTN_NO_ROPE = True                 # attn_fwd / attn_fwd_stats / attn_cls_fwd / attn_bwd(cos=None, sin=None): no rotary embedding, any Ntok > 1
     TOKEN_TAPS = True                   # tokens_to_nchw: the residual stream after a block as a [B, C, h, w] map (encode_dense(taps=), the detector backbone)
+    DECONV_ROWS = True                  # rows_to_nchw / nchw_to_rows: 2x2 transposed convolutions as GEMMs on token rows (neck.Deconv2x2)
 
     def __init__(self):
         self.lib = load_library()
@@ -600,6 +601,30 @@ class HipOps:
         assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == B * N and x.shape[1] >= C and N >= 2
         assert out.is_contiguous() and out.dim() == 4 and out.shape[0] == B and out.shape[1] == C and out.shape[2] * out.shape[3] == N - 1
         self._ok(self.lib.cs_transpose_bf16(_p(x), x.stride(0), _p(out), N - 1, N - 1, C, 1 + _dt(out), B, self._stream()), "cs_transpose_bf16")
+
+    @staticmethod
+    def _deconv_form(form, rows, nchw, B, h, w, C, s, off):
+        """Checks shared by rows_to_nchw / nchw_to_rows -> the packed `form` of cs_transpose_bf16 (include/clipself_hip.h)."""
+        assert s in (1, 2) and off in (0, 1) and min(B, h, w, C) >= 1 and w < (1 << 19)
+        assert rows.dim() == 2 and rows.stride(1) == 1 and rows.shape[0] == B * (h * w + off) and rows.shape[1] >= s * s * C <= rows.stride(0)
+        assert nchw.is_contiguous() and tuple(nchw.shape) == (B, C, s * h, s * w)
+        return form | (s - 1) << 8 | off << 9 | _dt(rows) << 10 | _dt(nchw) << 11 | w << 12
+
+    def rows_to_nchw(self, rows, B, h, w, C, s, off, out):
+        """rows fp32 / bf16 [B*(h*w + off), >= s*s*C] (row stride ld) -> out [B, C, s*h, s*w] contiguous, fp32 or bf16 (RNE):
+        out[b, c, s*i + di, s*j + dj] = rows[b*(h*w + off) + off + i*w + j, (di*s + dj)*C + c] -- form 4 of cs_transpose_bf16: the output
+        permutation of a transposed convolution with kernel == stride == s run as a GEMM on token rows (s = 1: rows back to a map)."""
+        self._chk(rows, out)
+        form = self._deconv_form(4, rows, out, B, h, w, C, s, off)
+        self._ok(self.lib.cs_transpose_bf16(_p(rows), rows.stride(0), _p(out), 0, h * w, C, form, B, self._stream()), "cs_transpose_bf16")
+
+    def nchw_to_rows(self, x, B, h, w, C, s, off, rows):
+        """The inverse, form 5: x fp32 / bf16 [B, C, s*h, s*w] contiguous -> rows bf16 (RNE) [B*(h*w + off), >= s*s*C]; with off = 1 each
+        image's CLS row gets s*s*C zeros.  Columns past s*s*C are left alone."""
+        self._chk(x, rows)
+        assert rows.dtype == torch.bfloat16
+        form = self._deconv_form(5, rows, x, B, h, w, C, s, off)
+        self._ok(self.lib.cs_transpose_bf16(_p(x), 0, _p(rows), rows.stride(0), h * w, C, form, B, self._stream()), "cs_transpose_bf16")
 
     def transpose_bf16_batched(self, pairs):
         """[(inp [R, C], out [C, ld_out >= R]), ...] -> every out = inp^T (zero padded) in ONE launch.  The device descriptor table is

@@ -206,14 +206,16 @@ class EVAVisionTower(_Node):
             return feats.reshape(x.shape[0], g, g, -1).permute(0, 3, 1, 2)
         return feats
 
-    def forward_intermediates(self, x, out_indices, final_map: bool = True, dtype=torch.float32):
+    def forward_intermediates(self, x, out_indices, final_map: bool = True, dtype=torch.float32, rows=()):
         """One frozen pass for a detector backbone (F-ViT/models/evaclip_vit.py:61-106): the residual stream after the blocks `out_indices`
         (ascending; layers - 1 = the output of the last block's attention-free form) as [B, width, h, w] maps of `dtype` (fp32 or bf16), and
         the L2-normalised dense map as [B, E, h, w] -- the values of encode_dense(keep_shape=True) -- or None with final_map=False, which
-        also skips the final norm and the head.  Runs under no_grad whatever the tower's training state; outputs are detached."""
+        also skips the final norm and the head.  rows: positions within out_indices delivered as neck.TokenRows (the bf16 stream as it
+        is, for a Deconv2x2) instead of a map.  Runs under no_grad whatever the tower's training state; outputs are detached."""
         with torch.no_grad():
             x = x.to(self.engine.device)
-            dense, g, maps = self.engine.encode_dense(x, need_grad=False, taps=tuple(out_indices), final=final_map, tap_dtype=dtype)
+            dense, g, maps = self.engine.encode_dense(x, need_grad=False, taps=tuple(out_indices), final=final_map, tap_dtype=dtype,
+                                                       tap_rows=tuple(rows))
             fmap = dense[:, 1:].reshape(x.shape[0], g, g, -1).permute(0, 3, 1, 2) if final_map else None
         return maps, fmap
 

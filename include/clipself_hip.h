@@ -238,7 +238,19 @@ int cs_cast_f32_bf16(const float* x, void* y, long n, cs_stream_t stream);
  * each with its CLS row first and R = h * w patch rows behind it; out = [batch, Cc, R] contiguous (ld_out == R), fp32 (form 1) or bf16
  * (form 2, round to nearest even): out[b, c, p] = x[b * (R + 1) + 1 + p, c].  Any R >= 1, Cc >= 1, ld_in >= Cc; the CLS rows and the
  * columns [Cc, ld_in) are never read.  16-byte accesses where ld_in % 4 == 0 / R % 4 (fp32) or R % 8 (bf16) == 0 and the pointers are
- * 16-byte aligned, one element per lane otherwise.  Plain loads and stores, no workspace. */
+ * 16-byte aligned, one element per lane otherwise.  Plain loads and stores, no workspace.
+ * forms 4 / 5 (the LOW BYTE of `form`), a transposed convolution with kernel == stride == s as a GEMM on token rows (the detector neck,
+ * clipself_amd/neck.py): with P = h * w, `off` CLS rows in front of each image's P rows and q = di * s + dj,
+ *     nchw[b, c, s*i + di, s*j + dj]  <->  rows[b * (P + off) + off + i*w + j, q * C + c]
+ * form 4 copies rows -> nchw (in = rows, ld_in = its stride; out contiguous [batch, C, s*h, s*w], ld_out ignored), form 5 nchw -> rows
+ * (in contiguous, ld_in ignored; out = rows, ld_out = its stride) and, with off == 1, writes s*s*C zeros into each image's CLS row so
+ * that a weight gradient contracted over all rows is right.  The other bits of `form`: bit 8 = s - 1 (s in {1, 2}), bit 9 = off,
+ * bit 10 = element type of the rows (0 fp32, 1 bf16; form 5 writes bf16 only), bit 11 = element type of the NCHW tensor, bits 12-31 =
+ * the grid width w.  R = h * w (a multiple of w; h != w is fine), Cc = C, batch = B, any of them >= 1, batch * s <= 65535, rows stride
+ * >= s*s*C.  fp32 -> bf16 rounds to nearest even, bf16 -> fp32 is exact.  Form 4 never reads CLS rows or columns past s*s*C, form 5
+ * never writes columns past s*s*C.  16-byte accesses on the rows side where the stride and C are multiples of 4 (fp32) / 8 (bf16), on the
+ * NCHW side where s*w is, with 16-byte aligned pointers; one element per lane otherwise.  Plain loads and stores, no workspace.
+ * Any other form (3, or a low byte above 5) returns -1. */
 int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, cs_stream_t stream);
 /* `count` such transposes in one launch (the W^T shadows the dgrad GEMMs read are rebuilt after every AdamW step: eva_vit_model.py:99-103,
  * 177-179,218-219 are the linears; 49 matrices per step for B/16).  desc = DEVICE array of 48-byte records
