@@ -439,11 +439,7 @@ class EvaEngine(TowerEngine):
         Wp, cp, dp = f["proj"]
         part_x = ops.empty(((C + 63) // 64, M, 2), F32)
         xb2 = xb if (lo is not None and not first) else ops.empty((M, C), BF16)
-        if lo is not None:
-            ops.gemm_nt_ln_split(att, Wp, xb2, lo, dp, mean, rstd, cp, x_in=x if first else None, stats_part=part_x)
-        else:
-            ops.gemm_nt_ln(att, Wp, x, bias=dp, extra=x, ln_mean=mean, ln_rstd=rstd, ln_colsum=cp, stats_part=part_x, xb_out=xb2,
-                           epi=EPI_RESID_LN_F32)
+        self._resid_gemm_folded(att, Wp, dp, (mean, rstd, cp), x, xb2, lo, part_x, first=first)
         mean2, rstd2 = ops.empty((M,), F32), ops.empty((M,), F32)
         ops.ln_stats_finalize(part_x, 64, C, mean2, rstd2, eps)
         W12, c12, d12 = f["w12"]
@@ -453,17 +449,9 @@ class EvaEngine(TowerEngine):
                        group=Hd)
         ops.ln_stats_finalize(part_h, 32, Hl, mean, rstd, eps)
         W3, c3, d3 = f["w3"]
-        if lo is not None:
-            if not emit_next:
-                ops.gemm_nt_ln_split(hid, W3, xb2, lo, d3, mean, rstd, c3, x_out=x)
-                return None, None
-            ops.gemm_nt_ln_split(hid, W3, xb2, lo, d3, mean, rstd, c3, stats_part=part_x)
-        else:
-            if not emit_next:
-                ops.gemm_nt_ln(hid, W3, x, bias=d3, extra=x, ln_mean=mean, ln_rstd=rstd, ln_colsum=c3, epi=EPI_RESID_LN_F32)
-                return None, None
-            ops.gemm_nt_ln(hid, W3, x, bias=d3, extra=x, ln_mean=mean, ln_rstd=rstd, ln_colsum=c3, stats_part=part_x, xb_out=xb2,
-                           epi=EPI_RESID_LN_F32)
+        self._resid_gemm_folded(hid, W3, d3, (mean, rstd, c3), x, xb2, lo, part_x, last=not emit_next)
+        if not emit_next:
+            return None, None
         ops.ln_stats_finalize(part_x, 64, C, mean2, rstd2, eps)
         return xb2, (mean2, rstd2)
 

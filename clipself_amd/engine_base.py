@@ -35,7 +35,9 @@ def is_no_decay(name: str, ndim: int) -> bool:
 
 class TowerEngine:
     """A family supplies, besides its layout (`_layout`), stem (`_stem`, `_stem_bwd`), blocks (`_block_fwd`, `_teacher_block_folded`,
-    `_block_fwd_cls`, `_block_bwd`), `rope_tables`, `sync_transposed` and `_build_folds`:
+    `_block_fwd_cls`, `_block_bwd`), `rope_tables`, `sync_transposed` and `_build_folds` -- each family writes the half of its block behind
+    the attention core once (engine.py: `_block_post`, engine_openai.py: `block_fwd_mlp`), and both `_teacher_block_folded` issue their
+    residual GEMMs through `_resid_gemm_folded` here:
       names    BLOCK_TAG, FINAL_NORM, RESID_BIAS, _pos_table(views)
       head     _head (forward), _head_dgrad, _head_wgrad (the train-all weight / bias gradients)
       teacher  _fold_pass (does this pass fold?), _cls_block_folds, _lo_plane (is the low plane of the split stream allocated?)
@@ -396,6 +398,33 @@ class TowerEngine:
 
     def _cls_block_folds(self) -> bool:
         return True
+
+    def _identity_stats(self, M, C):
+        """(mean = 0 [M], rstd = 1 [M], column sums = 0 [C]): statistics under which a folded-LayerNorm epilogue is the plain one, bit for bit."""
+        key = ("ident", M, C)
+        if key not in self._tables:
+            self._tables[key] = (torch.zeros(M, dtype=F32, device=self.device), torch.ones(M, dtype=F32, device=self.device),
+                                 torch.zeros(C, dtype=F32, device=self.device))
+        return self._tables[key]
+
+    def _resid_gemm_folded(self, A, W, bias, ln, x, xb, lo, part, first=False, last=False):
+        """A residual GEMM of _teacher_block_folded: stream += LN(A) . W^T + bias with the LayerNorm folded -- ln = its (mean, rstd, column
+        sums of gamma (.) W), or None where the family has no LayerNorm in front of this GEMM.  The stream is fp32 x, or with lo the planes
+        (xb, lo): read from x by the first residual GEMM of the tower, written back to x by the last.  Every one but the last also leaves the
+        bf16 copy xb of the new stream and the partial row statistics `part` for the next folded GEMM."""
+        ops = self.ops
+        if lo is not None:
+            mean, rstd, colsum = ln if ln is not None else self._identity_stats(*x.shape)
+            if last:
+                ops.gemm_nt_ln_split(A, W, xb, lo, bias, mean, rstd, colsum, x_out=x)
+            else:
+                ops.gemm_nt_ln_split(A, W, xb, lo, bias, mean, rstd, colsum, x_in=x if first else None, stats_part=part)
+        elif last and ln is None:                                       # nothing folded, nothing emitted: the plain residual GEMM
+            ops.gemm_nt(A, W, x, bias=bias, extra=x, epi=EPI_RESID_F32)
+        else:
+            mean, rstd, colsum = ln if ln is not None else (None, None, None)
+            ops.gemm_nt_ln(A, W, x, bias=bias, extra=x, ln_mean=mean, ln_rstd=rstd, ln_colsum=colsum, stats_part=None if last else part,
+                           xb_out=None if last else xb, epi=EPI_RESID_LN_F32 if ln is not None else EPI_RESID_F32)
 
     def encode_image(self, images, chunk: int = 256):
         """Frozen-teacher path: full ViT, final LN on the CLS row, head.  [K,3,S,S] -> fp32 [K,E].

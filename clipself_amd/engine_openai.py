@@ -17,6 +17,10 @@ does each stage (paths under /root/reference/src/open_clip/):
 The frozen teacher runs TowerEngine.encode_image like the EVA02 one: CLS-query-only last block, ln_1 / ln_2 folded into the in_proj / c_fc
 GEMMs with the residual GEMMs emitting the bf16 copy and the row statistics of the stream (`_teacher_block_folded`).
 
+The block's forward behind the attention core -- out_proj (+x), ln_2, c_fc + activation, c_proj (+x1) -- is written once, in block_fwd_mlp
+below (the twin of _block_bwd_mlp): every row set of this engine runs it (image tokens, the CLS rows, mask-attention passengers) and so
+does the text tower (engine_text.py).
+
 Differences to the EVA02 schedule: no RoPE (the attention kernels run without tables: rope_tables), no sub-LayerNorms, `proj` is a bias-free
 [C,E] matrix kept transposed for the forward GEMM, and the last dense block owns no never-reached *tensor* (q/k are rows of the one
 in_proj_weight parameter, whose gradient rows stay zero -- exactly what autograd hands torch's AdamW).
@@ -49,6 +53,38 @@ def clip_vit_layout(cfg: TowerCfg, prefix: str = "visual."):
                    [t(b + "mlp.c_proj.weight", (C, Hd))], [t(b + "mlp.c_proj.bias", (C,))]]
     groups += [[t(prefix + "ln_post.weight", (C,))], [t(prefix + "ln_post.bias", (C,))], [t(prefix + "proj", (C, E))]]
     return groups
+
+
+def act_epilogue(quick_gelu: bool):
+    """The GEMM epilogue that applies this family's MLP activation (transformer.py:31-34,209-213)."""
+    return EPI_QGELU_BF16 if quick_gelu else EPI_GELU_BF16
+
+
+def block_fwd_mlp(ops, p, w, b, eps, quick_gelu, x, att, save=None, inplace=True):
+    """Row-wise half of a block's forward behind the attention core: x1 = x + out_proj(att), x2 = x1 + c_proj(act(c_fc(ln_2 x1))) -> x2.
+    p / w: fp32 parameters and bf16 matrices by name, b: the block's name prefix, x fp32 [rows, C], att bf16 [rows, C].  inplace: x1 and x2
+    are x itself.  save (dict): the activations _block_bwd_mlp needs are kept and put into it -- c_fc's output before the activation
+    (fc, hence the separate activation pass) and ln_2's row statistics; otherwise the activation is c_fc's epilogue."""
+    R, C = x.shape
+    Hd = w[b + "mlp.c_fc.weight"].shape[0]
+    keep = save is not None
+    x1 = x if inplace else ops.empty((R, C), F32)
+    ops.gemm_nt(att, w[b + "attn.out_proj.weight"], x1, bias=p[b + "attn.out_proj.bias"], extra=x, epi=EPI_RESID_F32)
+    ln2 = ops.empty((R, C), BF16)
+    m2, r2 = (ops.empty((R,), F32), ops.empty((R,), F32)) if keep else (None, None)
+    ops.layernorm_fwd(x1, p[b + "ln_2.weight"], p[b + "ln_2.bias"], ln2, m2, r2, eps)
+    hid = ops.empty((R, Hd), BF16)
+    if keep:
+        fc = ops.empty((R, Hd), BF16)
+        ops.gemm_nt(ln2, w[b + "mlp.c_fc.weight"], fc, bias=p[b + "mlp.c_fc.bias"], epi=EPI_BF16)
+        ops.gelu_fwd(fc, hid, quick_gelu)
+    else:
+        ops.gemm_nt(ln2, w[b + "mlp.c_fc.weight"], hid, bias=p[b + "mlp.c_fc.bias"], epi=act_epilogue(quick_gelu))
+    x2 = x1 if inplace else ops.empty((R, C), F32)
+    ops.gemm_nt(hid, w[b + "mlp.c_proj.weight"], x2, bias=p[b + "mlp.c_proj.bias"], extra=x1, epi=EPI_RESID_F32)
+    if keep:
+        save.update(x1=x1, ln2=ln2, st2=(m2, r2), fc=fc, hid=hid)
+    return x2
 
 
 class ClipVitEngine(TowerEngine):
@@ -184,16 +220,19 @@ class ClipVitEngine(TowerEngine):
         ops.layernorm_fwd_f32(x.view(B * N, C), self.p[P + "ln_pre.weight"], self.p[P + "ln_pre.bias"], y.view(B * N, C), mean, rstd, cfg.ln_eps)
         return y, g
 
+    def _block_fwd_mlp(self, b, x, att, save=None, inplace=True):
+        """block_fwd_mlp on this tower's parameters: the forward twin of _block_bwd_mlp, for whichever rows x holds."""
+        return block_fwd_mlp(self.ops, self.p, self.w, b, self.cfg.ln_eps, self.cfg.quick_gelu, x, att, save, inplace)
+
     def _block_fwd(self, i, x, B, N, cos, sin, with_attn=True, save=None, inplace=True):
         ops, cfg = self.ops, self.cfg
-        C, Hd, H, eps = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps
+        C, H, eps = cfg.width, cfg.heads, cfg.ln_eps
         b = f"{self.prefix}{self.BLOCK_TAG}{i}."
         M = B * N
         keep = save is not None
-        st = (lambda: (ops.empty((M,), F32), ops.empty((M,), F32))) if keep else (lambda: (None, None))
 
         ln1 = ops.empty((M, C), BF16)
-        m1, r1 = st()
+        m1, r1 = (ops.empty((M,), F32), ops.empty((M,), F32)) if keep else (None, None)
         ops.layernorm_fwd(x, self.p[b + "ln_1.weight"], self.p[b + "ln_1.bias"], ln1, m1, r1, eps)
         wqkv, bqkv = self.w[b + "attn.in_proj_weight"], self.p[b + "attn.in_proj_bias"]
         qkv = lse = None
@@ -205,27 +244,9 @@ class ClipVitEngine(TowerEngine):
             ops.attn_fwd(qkv, cos, sin, att, lse, B, N, H, cfg.head_width ** -0.5)
         else:
             ops.gemm_nt(ln1, wqkv[2 * C:], att, bias=bqkv[2 * C:], epi=EPI_BF16)        # proj_without_attn: the value rows only
-        x1 = x if inplace else ops.empty((M, C), F32)
-        ops.gemm_nt(att, self.w[b + "attn.out_proj.weight"], x1, bias=self.p[b + "attn.out_proj.bias"], extra=x, epi=EPI_RESID_F32)
-
-        ln2 = ops.empty((M, C), BF16)
-        m2, r2 = st()
-        ops.layernorm_fwd(x1, self.p[b + "ln_2.weight"], self.p[b + "ln_2.bias"], ln2, m2, r2, eps)
-        hid = ops.empty((M, Hd), BF16)
-        fc = None
         if keep:
-            fc = ops.empty((M, Hd), BF16)
-            ops.gemm_nt(ln2, self.w[b + "mlp.c_fc.weight"], fc, bias=self.p[b + "mlp.c_fc.bias"], epi=EPI_BF16)
-            ops.gelu_fwd(fc, hid, cfg.quick_gelu)
-        else:
-            ops.gemm_nt(ln2, self.w[b + "mlp.c_fc.weight"], hid, bias=self.p[b + "mlp.c_fc.bias"],
-                        epi=EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16)
-        x2 = x1 if inplace else ops.empty((M, C), F32)
-        ops.gemm_nt(hid, self.w[b + "mlp.c_proj.weight"], x2, bias=self.p[b + "mlp.c_proj.bias"], extra=x1, epi=EPI_RESID_F32)
-        if keep:
-            save.update(x0=x, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, att=att, with_attn=with_attn, x1=x1, ln2=ln2, st2=(m2, r2),
-                        fc=fc, hid=hid)
-        return x2
+            save.update(x0=x, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, att=att, with_attn=with_attn)
+        return self._block_fwd_mlp(b, x, att, save, inplace)
 
     def _teacher_block_folded(self, i, x, xb, st, B, N, cos, sin, emit_next, lo=None):
         """One frozen-tower block with both LayerNorms folded into the GEMMs (in place on x).  xb / st = bf16 copy and (mean, rstd) of x as
@@ -233,7 +254,7 @@ class ClipVitEngine(TowerEngine):
         emit_next.  With lo (int16 [M, C]; round 4) the stream lives in the two 16-bit planes (xb, lo) between the first residual GEMM of
         the tower, which reads fp32 x, and the last one (emit_next False), which writes fp32 x again -- cs_gemm_nt_ln_split:
         8 instead of 10 bytes per stream element and residual GEMM, same fp32 values.  This family has no LayerNorm in front of
-        out_proj / c_proj, so the split kernel gets the identity statistics (mean 0, rstd 1, column sums 0: x + 1 * (acc - 0 * 0) + b)."""
+        out_proj / c_proj (ln=None of _resid_gemm_folded), so the split kernel gets the identity statistics (mean 0, rstd 1, column sums 0: x + 1 * (acc - 0 * 0) + b)."""
         ops, cfg = self.ops, self.cfg
         C, Hd, H, eps = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps
         b = f"{self.prefix}{self.BLOCK_TAG}{i}."
@@ -252,38 +273,17 @@ class ClipVitEngine(TowerEngine):
         ops.attn_fwd(qkv, cos, sin, att, None, B, N, H, cfg.head_width ** -0.5)
         part = ops.empty(((C + 63) // 64, M, 2), F32)
         xb2 = xb if (lo is not None and not first) else ops.empty((M, C), BF16)
-        ident = self._identity_stats(M, C) if lo is not None else None
-        wo, bo = self.w[b + "attn.out_proj.weight"], self.p[b + "attn.out_proj.bias"]
-        if lo is not None:
-            ops.gemm_nt_ln_split(att, wo, xb2, lo, bo, *ident, x_in=x if first else None, stats_part=part)
-        else:
-            ops.gemm_nt_ln(att, wo, x, bias=bo, extra=x, stats_part=part, xb_out=xb2, epi=EPI_RESID_F32)
+        self._resid_gemm_folded(att, self.w[b + "attn.out_proj.weight"], self.p[b + "attn.out_proj.bias"], None, x, xb2, lo, part, first=first)
         mean, rstd = ops.empty((M,), F32), ops.empty((M,), F32)
         ops.ln_stats_finalize(part, 64, C, mean, rstd, eps)
         Wf, cf, df = f["fc"]
         hid = ops.empty((M, Hd), BF16)
-        ops.gemm_nt_ln(xb2, Wf, hid, bias=df, ln_mean=mean, ln_rstd=rstd, ln_colsum=cf, epi=EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16)
-        wp, bp = self.w[b + "mlp.c_proj.weight"], self.p[b + "mlp.c_proj.bias"]
-        if lo is not None:
-            if not emit_next:
-                ops.gemm_nt_ln_split(hid, wp, xb2, lo, bp, *ident, x_out=x)
-                return None, None
-            ops.gemm_nt_ln_split(hid, wp, xb2, lo, bp, *ident, stats_part=part)
-        else:
-            if not emit_next:
-                ops.gemm_nt(hid, wp, x, bias=bp, extra=x, epi=EPI_RESID_F32)
-                return None, None
-            ops.gemm_nt_ln(hid, wp, x, bias=bp, extra=x, stats_part=part, xb_out=xb2, epi=EPI_RESID_F32)
+        ops.gemm_nt_ln(xb2, Wf, hid, bias=df, ln_mean=mean, ln_rstd=rstd, ln_colsum=cf, epi=act_epilogue(cfg.quick_gelu))
+        self._resid_gemm_folded(hid, self.w[b + "mlp.c_proj.weight"], self.p[b + "mlp.c_proj.bias"], None, x, xb2, lo, part, last=not emit_next)
+        if not emit_next:
+            return None, None
         ops.ln_stats_finalize(part, 64, C, mean, rstd, eps)
         return xb2, (mean, rstd)
-
-    def _identity_stats(self, M, C):
-        """(mean = 0 [M], rstd = 1 [M], column sums = 0 [C]): statistics under which a folded-LayerNorm epilogue is the plain one, bit for bit."""
-        key = ("ident", M, C)
-        if key not in self._tables:
-            self._tables[key] = (torch.zeros(M, dtype=F32, device=self.device), torch.ones(M, dtype=F32, device=self.device),
-                                 torch.zeros(C, dtype=F32, device=self.device))
-        return self._tables[key]
 
     def _block_fwd_cls(self, i, x, B, N, cos, sin, xb=None, st=None, lo=None):
         """Last teacher block restricted to what forward() consumes: the CLS row.  x fp32 [B*N, C] -> fp32 [B, C]; keys and values still
@@ -291,7 +291,7 @@ class ClipVitEngine(TowerEngine):
         (and low plane) the previous folded block left -- ln_1 is folded into the K|V GEMM like in every other block (no LayerNorm pass over
         the whole stream, which never returns to fp32) and only the B CLS rows are rebuilt in fp32."""
         ops, cfg = self.ops, self.cfg
-        C, Hd, H, eps = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps
+        C, H, eps = cfg.width, cfg.heads, cfg.ln_eps
         b = f"{self.prefix}{self.BLOCK_TAG}{i}."
         M = B * N
         wqkv, bqkv = self.w[b + "attn.in_proj_weight"], self.p[b + "attn.in_proj_bias"]
@@ -313,15 +313,17 @@ class ClipVitEngine(TowerEngine):
             xc = x.view(B, N, C)[:, 0, :].contiguous()
         att = ops.empty((B, C), BF16)
         ops.attn_cls_fwd(q, kv, cos, sin, att, B, N, H, cfg.head_width ** -0.5)
-        ops.gemm_nt(att, self.w[b + "attn.out_proj.weight"], xc, bias=self.p[b + "attn.out_proj.bias"], extra=xc, epi=EPI_RESID_F32)
-        ln2 = ops.empty((B, C), BF16)
-        ops.layernorm_fwd(xc, self.p[b + "ln_2.weight"], self.p[b + "ln_2.bias"], ln2, None, None, eps)
-        hid = ops.empty((B, Hd), BF16)
-        ops.gemm_nt(ln2, self.w[b + "mlp.c_fc.weight"], hid, bias=self.p[b + "mlp.c_fc.bias"], epi=EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16)
-        ops.gemm_nt(hid, self.w[b + "mlp.c_proj.weight"], xc, bias=self.p[b + "mlp.c_proj.bias"], extra=xc, epi=EPI_RESID_F32)
-        return xc
+        return self._block_fwd_mlp(b, xc, att)
 
     # ------------------------------------------------------------------------------------------ mask-attention pooling (inference)
+    def _allow_table(self, masks, B, Q, N, g):
+        """uint8 [B*Q, N], 1 = query q of image b may attend token n: the CLS token and the tokens inside its mask; padding queries see everything."""
+        allow = torch.ones((B, Q, N), dtype=torch.uint8, device=self.device)
+        for b, m in enumerate(masks):
+            assert tuple(m.shape[1:]) == (g, g), f"masks live on the {g}x{g} token grid, got {tuple(m.shape[1:])}"
+            allow[b, :m.shape[0], 1:] = m.flatten(1).to(device=self.device, dtype=torch.uint8)
+        return allow.view(B * Q, N)
+
     def mask_attn_pool(self, images, masks, chunk: int = 64, need_grad: bool = False):
         """VisionTransformer.mask_attn_pool / _mask_attn_pool (transformer.py:736-834), the pooling behind extract_type='v1' (:660-671) and
         encode_masks(mask_attn=True).  masks: list over images of bool [n_i, g, g] on the token grid.  Every mask is an extra token -- a copy
@@ -334,25 +336,20 @@ class ClipVitEngine(TowerEngine):
         if need_grad:
             return self._mask_attn_pool_train(images, masks)
         ops, cfg, P = self.ops, self.cfg, self.prefix
-        C, Hd, H, eps, E = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps, cfg.embed_dim
+        C, H, eps, E = cfg.width, cfg.heads, cfg.ln_eps, cfg.embed_dim
         counts = [int(m.shape[0]) for m in masks]
         assert len(masks) == images.shape[0], "one mask list per image"
         Q = max(counts) if counts else 0
         if Q == 0:                                   # no image has a mask: transformer.py:823-824 returns zero rows
             return torch.zeros((0, E), dtype=F32, device=self.device)
         outs = []                                    # an image WITHOUT masks is all padding: see-everything queries whose rows are dropped (:793-795)
-        act = EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16
         for k0 in range(0, images.shape[0], chunk):
             img = images[k0:k0 + chunk]
             B = img.shape[0]
             x, g = self._stem(img)
             N = g * g + 1
             cos, sin = self.rope_tables(g)
-            allow = torch.ones((B, Q, N), dtype=torch.uint8, device=self.device)
-            for b, m in enumerate(masks[k0:k0 + B]):
-                assert tuple(m.shape[1:]) == (g, g), f"masks live on the {g}x{g} token grid, got {tuple(m.shape[1:])}"
-                allow[b, :m.shape[0], 1:] = m.flatten(1).to(device=self.device, dtype=torch.uint8)
-            allow = allow.view(B * Q, N)
+            allow = self._allow_table(masks[k0:k0 + B], B, Q, N, g)
             xf = x.view(B * N, C)
             xm = x[:, :1, :].expand(B, Q, C).reshape(B * Q, C).contiguous()          # fp32 passenger stream
             MQ = B * Q
@@ -369,21 +366,11 @@ class ClipVitEngine(TowerEngine):
                 ops.gemm_nt(lnm, wqkv[:C], qm, bias=bqkv[:C], epi=EPI_BF16)
                 attm = ops.empty((MQ, C), BF16)
                 ops.attn_query_fwd(qm, qkv[:, C:], allow, attm, B, Q, N, H, cfg.head_width ** -0.5)
-                ops.gemm_nt(attm, self.w[b_ + "attn.out_proj.weight"], xm, bias=self.p[b_ + "attn.out_proj.bias"], extra=xm, epi=EPI_RESID_F32)
-                ln2 = ops.empty((MQ, C), BF16)
-                ops.layernorm_fwd(xm, self.p[b_ + "ln_2.weight"], self.p[b_ + "ln_2.bias"], ln2, None, None, eps)
-                hid = ops.empty((MQ, Hd), BF16)
-                ops.gemm_nt(ln2, self.w[b_ + "mlp.c_fc.weight"], hid, bias=self.p[b_ + "mlp.c_fc.bias"], epi=act)
-                ops.gemm_nt(hid, self.w[b_ + "mlp.c_proj.weight"], xm, bias=self.p[b_ + "mlp.c_proj.bias"], extra=xm, epi=EPI_RESID_F32)
+                self._block_fwd_mlp(b_, xm, attm)
                 if i + 1 < cfg.layers:                      # the image tokens move on (they never see the passengers); not needed after the last block
                     att = ops.empty((B * N, C), BF16)
                     ops.attn_fwd(qkv, cos, sin, att, None, B, N, H, cfg.head_width ** -0.5)
-                    ops.gemm_nt(att, self.w[b_ + "attn.out_proj.weight"], xf, bias=self.p[b_ + "attn.out_proj.bias"], extra=xf, epi=EPI_RESID_F32)
-                    ln2i = ops.empty((B * N, C), BF16)
-                    ops.layernorm_fwd(xf, self.p[b_ + "ln_2.weight"], self.p[b_ + "ln_2.bias"], ln2i, None, None, eps)
-                    hidi = ops.empty((B * N, Hd), BF16)
-                    ops.gemm_nt(ln2i, self.w[b_ + "mlp.c_fc.weight"], hidi, bias=self.p[b_ + "mlp.c_fc.bias"], epi=act)
-                    ops.gemm_nt(hidi, self.w[b_ + "mlp.c_proj.weight"], xf, bias=self.p[b_ + "mlp.c_proj.bias"], extra=xf, epi=EPI_RESID_F32)
+                    self._block_fwd_mlp(b_, xf, att)
             lnp = ops.empty((MQ, C), BF16)
             ops.layernorm_fwd(xm, self.p[P + "ln_post.weight"], self.p[P + "ln_post.bias"], lnp, None, None, eps)
             pooled = ops.empty((MQ, E), F32)
@@ -393,13 +380,6 @@ class ClipVitEngine(TowerEngine):
         return torch.cat(outs)
 
     # ------------------------------------------------------------------------------------------ mask-attention pooling (training)
-    def _allow_table(self, masks, B, Q, N, g):
-        allow = torch.ones((B, Q, N), dtype=torch.uint8, device=self.device)
-        for b, m in enumerate(masks):
-            assert tuple(m.shape[1:]) == (g, g), f"masks live on the {g}x{g} token grid, got {tuple(m.shape[1:])}"
-            allow[b, :m.shape[0], 1:] = m.flatten(1).to(device=self.device, dtype=torch.uint8)
-        return allow.view(B * Q, N)
-
     def _mask_attn_pool_train(self, images, masks):
         """mask_attn_pool() that keeps the activations of the trainable blocks (and of a trainable stem) for backward_mask_attn().  One row
         stream [B*N + B*Q, C] per block -- the image tokens, then the passengers -- so LayerNorm, the GEMMs and the activation stay single
@@ -407,7 +387,7 @@ class ClipVitEngine(TowerEngine):
         passengers, whose queries are the q columns of their rows of the q|k|v matrix).  The image tokens' output of the last block is
         consumed by nobody: after its q|k|v GEMM that block runs on the passenger rows alone."""
         ops, cfg, P = self.ops, self.cfg, self.prefix
-        C, Hd, H, eps, E = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps, cfg.embed_dim
+        C, H, eps, E = cfg.width, cfg.heads, cfg.ln_eps, cfg.embed_dim
         counts = [int(m.shape[0]) for m in masks]
         assert len(masks) == images.shape[0], "one mask list per image"
         Q = max(counts) if counts else 0
@@ -433,9 +413,8 @@ class ClipVitEngine(TowerEngine):
             keep = i >= self.first_trainable
             R0 = BN if last else 0                                  # first row that continues past the attention
             R = M - R0
-            st = (lambda n: (ops.empty((n,), F32), ops.empty((n,), F32))) if keep else (lambda n: (None, None))
             ln1 = ops.empty((M, C), BF16)
-            m1, r1 = st(M)
+            m1, r1 = (ops.empty((M,), F32), ops.empty((M,), F32)) if keep else (None, None)
             ops.layernorm_fwd(xs, self.p[b_ + "ln_1.weight"], self.p[b_ + "ln_1.bias"], ln1, m1, r1, eps)
             qkv = ops.empty((M, 3 * C), BF16)
             ops.gemm_nt(ln1, self.w[b_ + "attn.in_proj_weight"], qkv, bias=self.p[b_ + "attn.in_proj_bias"], epi=EPI_BF16)
@@ -446,27 +425,9 @@ class ClipVitEngine(TowerEngine):
                 ops.attn_fwd(qkv[:BN], cos, sin, att[:BN], lse, B, N, H, scale)
             lse_m = ops.empty((B * H, Q), F32) if keep else None
             ops.attn_query_fwd(qkv[BN:, :C], qkv[:BN, C:], allow, att[BN - R0:], B, Q, N, H, scale, **(dict(lse=lse_m) if keep else {}))
-            xin = xs[R0:]
-            x1 = ops.empty((R, C), F32) if keep else xin
-            ops.gemm_nt(att, self.w[b_ + "attn.out_proj.weight"], x1, bias=self.p[b_ + "attn.out_proj.bias"], extra=xin, epi=EPI_RESID_F32)
-            ln2 = ops.empty((R, C), BF16)
-            m2, r2 = st(R)
-            ops.layernorm_fwd(x1, self.p[b_ + "ln_2.weight"], self.p[b_ + "ln_2.bias"], ln2, m2, r2, eps)
-            hid = ops.empty((R, Hd), BF16)
-            fc = None
             if keep:
-                fc = ops.empty((R, Hd), BF16)
-                ops.gemm_nt(ln2, self.w[b_ + "mlp.c_fc.weight"], fc, bias=self.p[b_ + "mlp.c_fc.bias"], epi=EPI_BF16)
-                ops.gelu_fwd(fc, hid, cfg.quick_gelu)
-            else:
-                ops.gemm_nt(ln2, self.w[b_ + "mlp.c_fc.weight"], hid, bias=self.p[b_ + "mlp.c_fc.bias"],
-                            epi=EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16)
-            x2 = ops.empty((R, C), F32) if keep else x1
-            ops.gemm_nt(hid, self.w[b_ + "mlp.c_proj.weight"], x2, bias=self.p[b_ + "mlp.c_proj.bias"], extra=x1, epi=EPI_RESID_F32)
-            if keep:
-                saves[i] = dict(x0=xs, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, lse_m=lse_m, att=att, with_attn=True, x1=x1, ln2=ln2,
-                                st2=(m2, r2), fc=fc, hid=hid, R0=R0)
-            xs = x2
+                saves[i] = dict(x0=xs, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, lse_m=lse_m, att=att, with_attn=True, R0=R0)
+            xs = self._block_fwd_mlp(b_, xs[R0:], att, saves.get(i), inplace=not keep)
         xm = xs                                                      # [B*Q, C]: what the last block left
         lnp = ops.empty((MQ, C), BF16)
         mean, rstd = ops.empty((MQ,), F32), ops.empty((MQ,), F32)

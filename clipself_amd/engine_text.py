@@ -2,8 +2,8 @@
 family's `model.text`) and the text half of open_clip's CLIP (model.py:199-212,269-281) on the kernels of the vision towers.
 
   embedding   transformer.py:724-726   token_embedding(ids) + positional_embedding            (torch row gather: glue)
-  block       transformer.py:232-244   x += out_proj(MHA(ln_1 x, causal mask)); x += c_proj(act(c_fc(ln_2 x)))   -- the layout of
-                                       ClipVitEngine._block_fwd: LayerNorm eps 1e-5, fused in_proj, GELU / QuickGELU
+  block       transformer.py:232-244   x += out_proj(MHA(ln_1 x, causal mask)); x += c_proj(act(c_fc(ln_2 x)))   -- the OpenAI-CLIP
+                                       block with LayerNorm eps 1e-5: what follows the attention is engine_openai.block_fwd_mlp
   attention   transformer.py:714-720   additive triu(-inf) mask = causal self-attention: ops.attn_query_fwd(allow=None)
   head        transformer.py:731-736   ln_final(x)[arange, ids.argmax(-1)] @ text_projection
 
@@ -16,7 +16,8 @@ from __future__ import annotations
 import torch
 
 from .config import TowerCfg
-from .engine_base import BF16, EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_QGELU_BF16, EPI_RESID_F32, F32
+from .engine_base import BF16, EPI_BF16, EPI_F32, F32
+from .engine_openai import block_fwd_mlp
 
 LN_EPS = 1e-5                     # nn.LayerNorm default: the text towers of both families (transformer.py:52-58)
 MAX_CONTEXT = 128                 # cs_attn_query_fwd(allow=NULL)
@@ -80,7 +81,8 @@ class TextEngine:
         self._key = key
 
     def _block(self, i, x, B, L):
-        """transformer.py:232-244 in place on the fp32 stream x [B*L, W]; ClipVitEngine._block_fwd's schedule with the causal attention."""
+        """transformer.py:232-244 in place on the fp32 stream x [B*L, W]: ln_1, in_proj and the causal attention here, the rest of the
+        block is engine_openai.block_fwd_mlp, shared with the vision tower."""
         ops, cfg, p, w = self.ops, self.cfg, self.p, self.w
         W, H, M = cfg.text_width, cfg.text_heads, B * L
         b = f"transformer.resblocks.{i}."
@@ -90,12 +92,7 @@ class TextEngine:
         ops.gemm_nt(ln1, w[b + "attn.in_proj_weight"], qkv, bias=p[b + "attn.in_proj_bias"], epi=EPI_BF16)
         att = ops.empty((M, W), BF16)
         ops.attn_query_fwd(qkv[:, :W], qkv[:, W:], None, att, B, L, L, H, 64 ** -0.5)
-        ops.gemm_nt(att, w[b + "attn.out_proj.weight"], x, bias=p[b + "attn.out_proj.bias"], extra=x, epi=EPI_RESID_F32)
-        ln2 = ops.empty((M, W), BF16)
-        ops.layernorm_fwd(x, p[b + "ln_2.weight"], p[b + "ln_2.bias"], ln2, None, None, LN_EPS)
-        hid = ops.empty((M, 4 * W), BF16)
-        ops.gemm_nt(ln2, w[b + "mlp.c_fc.weight"], hid, bias=p[b + "mlp.c_fc.bias"], epi=EPI_QGELU_BF16 if cfg.quick_gelu else EPI_GELU_BF16)
-        ops.gemm_nt(hid, w[b + "mlp.c_proj.weight"], x, bias=p[b + "mlp.c_proj.bias"], extra=x, epi=EPI_RESID_F32)
+        block_fwd_mlp(ops, p, w, b, LN_EPS, cfg.quick_gelu, x, att)
 
     @torch.no_grad()
     def encode(self, text, trim: bool = True, chunk: int = 4096):
