@@ -18,6 +18,13 @@
 //     a cursor keeps cycling over that tile's K tiles: valid memory, slots nobody reads), the cursor advance sits behind the MFMAs, and the
 //     six ds_read_b128 of k-step ks+1 go one behind each of the first six MFMAs of k-step ks (two fragment register sets,
 //     sched_group_barrier); left to itself hipcc clusters reads and MFMAs into runs of 2-4 with lgkmcnt(0) between them.
+//   * Round 7: the frozen tower's folded-LN register-epilogue launches (q|k|v, W1|W2, QuickGELU c_fc) run the K loop on
+//     v_mfma_f32_16x16x32_bf16 (template parameter MF = 16, ktile_m16): same tile, LDS image, rings, roles and barrier, 8 x 4 accumulator
+//     blocks of 16x16 per wave, a lane owns row (lane & 15) of a block and four consecutive columns 4*(lane >> 4) + r; the epilogues
+//     (epi_bf16_m16, epi_swiglu_m16) pair lane rows with v_permlane16_swap for the same 16-byte stores.  The loop takes ~5 % MORE cycles
+//     than the 32x32x16 one and the chip holds a ~9 % higher clock on it: q|k|v 1369 -> 1334 us, W1|W2 2414 -> 2271 us at the step's
+//     launch shapes (profiles/r07_a_mfma16_ab.txt).  Everything else stays on 32x32x16: the !LN kernels and 192-row tiles (tied bit for
+//     bit to one another by tests), the slab epilogues (241-252 VGPRs already), fp8.  CS_GEMM_MFMA32=1 selects the old loop (A/B switch).
 //   * The epilogue's stores are never waited for: vmcnt retires in order on gfx9, so the first K tile after an epilogue waits
 //     vmcnt(4 + S) with S = the fixed number of store instructions an epilogue issues (buffer stores with out-of-range offsets for
 //     masked rows / columns keep that count exact).
@@ -55,6 +62,12 @@ __device__ __forceinline__ void swap32(unsigned& x, unsigned& y) {
     x = r[0];
     y = r[1];
 }
+// row exchange (a row = 16 lanes): rows 1, 3 of x <-> rows 0, 2 of y (v_permlane16_swap)
+__device__ __forceinline__ void swap16(unsigned& x, unsigned& y) {
+    const u32x2 r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+    x = r[0];
+    y = r[1];
+}
 __device__ __forceinline__ float both_halves(float v) {                     // v(lane) + v(lane ^ 32)
     const u32x2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
@@ -88,10 +101,12 @@ __device__ __forceinline__ float activate_s(float v) {
 
 // Epilogue operands that do not depend on the accumulators: per-row LayerNorm statistics of the wave's four 32-row blocks (lane = row)
 // and the per-column constants of its 64 columns (lane = column).
-struct EpiOps {
-    float mean[4], rstd[4];
+template <int NB>
+struct EpiOpsT {
+    float mean[NB], rstd[NB];
     float cb, cc;            // bias / folded-LN column sum of column (lane) -- SwiGLU: lanes 0-31 = x1 columns, 32-63 = x2 columns
 };
+typedef EpiOpsT<4> EpiOps;
 
 // ---------------------------------------------------------------------------------------------------------------- SwiGLU
 // acc[i][0] = x1, acc[i][1] = x2 of hidden units hbase + col(e, lane>>5); out[row][hidden] = silu(x1) * x2 in bf16.
@@ -222,6 +237,157 @@ __device__ __forceinline__ void epi_bf16(const GemmArgs& p, const f32x16 (&acc)[
                 swap32(x1, y1);
                 store16<CP>(u32x4{x0, x1, y0, y1}, rc, ok ? rowoff + 32u * pr : OOB);
             }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- 16x16x32 accumulators
+// MF = 16 (see gemm_stream_kernel): the wave tile is 8 x 4 blocks of 16x16, acc[i][j][r] = row i*16 + (lane & 15), column
+// j*16 + 4*(lane >> 4) + r.  A lane holds 8 bytes of bf16 per block; v_permlane16_swap pairs the lane rows g and g ^ 1 across the row
+// blocks 2t and 2t+1 (swap32 one level down): even rows keep block 2t and store its columns 4g .. 4g+7, odd rows block 2t+1, columns
+// 4(g-1) .. 4(g-1)+7 -- 16 bytes per lane, 16 store instructions per wave as in the 32x32 form.  Same arithmetic per element.
+template <int ACT, bool LN, int CP>
+__device__ __forceinline__ void epi_bf16_m16(const GemmArgs& p, const f32x4 (&acc)[8][4], int lane, int row0, int colw, const EpiOpsT<8>& eo) {
+    const int l15 = lane & 15, g = lane >> 4;
+    float nm[8], rs[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        rs[i] = LN ? eo.rstd[i] : 1.f;
+        nm[i] = LN ? -eo.rstd[i] * eo.mean[i] : 0.f;
+    }
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc((const __bf16*)p.C + (size_t)row0 * p.ldc + colw);
+    const int sl0 = g << 4;                                             // byte address of source lane 4*g
+    unsigned pk[4][8][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float b[4], c[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int sl = sl0 + ((j * 16 + r) << 2);
+            b[r] = lane_bcast(sl, eo.cb);
+            c[r] = LN ? lane_bcast(sl, eo.cc) : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float ov[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ov[r] = activate_s<ACT>(LN ? fmaf(rs[i], acc[i][j][r], fmaf(nm[i], c[r], b[r])) : acc[i][j][r] + b[r]);
+            pk[j][i][0] = pack2(ov[0], ov[1]);
+            pk[j][i][1] = pack2(ov[2], ov[3]);
+        }
+        __builtin_amdgcn_sched_barrier(0);       // one column block at a time: its 32 accumulators become 16 packed registers before the next one's constants arrive
+    }
+    // stores in row-block order: the four 32-byte pieces of a row's 128-byte line leave back to back
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int rrel = (2 * t + (g & 1)) * 16 + l15;
+        const bool rowok = row0 + rrel < p.M && !CS_ABL(p, 8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool ok = rowok && colw + j * 16 < p.N;                     // wave-uniform column test: N % 32 == 0
+            unsigned x0 = pk[j][2 * t][0], x1 = pk[j][2 * t][1], y0 = pk[j][2 * t + 1][0], y1 = pk[j][2 * t + 1][1];
+            swap16(x0, y0);              // even rows: own block 2t | the odd row's block 2t     = columns 4g .. 4g+7
+            swap16(x1, y1);              // odd rows: the even row's block 2t+1 | own block 2t+1 = columns 4(g-1) .. 4(g-1)+7
+            store16<CP>(u32x4{x0, x1, y0, y1}, rc, ok ? (unsigned)(rrel * p.ldc + j * 16 + 8 * (g >> 1)) * 2u : OOB);
+        }
+    }
+}
+
+// SwiGLU on the 16x16 blocks: acc[i][j] = x1, acc[i][j + 2] = x2 of hidden units hbase + j*16 + 4*(lane >> 4) + r (j = 0, 1).  Same stores as
+// epi_bf16_m16 (two 16-column blocks); a row's 32 units sit in the four lanes l, l+16, l+32, l+48.
+template <bool LN, bool AUX, int CP>
+__device__ __forceinline__ void epi_swiglu_m16(const GemmArgs& p, const f32x4 (&acc)[8][4], int lane, int row0, int tn, int wn, const EpiOpsT<8>& eo) {
+    const int l15 = lane & 15, g = lane >> 4;
+    const int hbase = tn * 128 + wn * 32;
+    const bool colok = hbase < p.group;                                 // wave-uniform: group % 32 == 0 (checked by the launcher)
+    float nm[8], rs[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        rs[i] = LN ? eo.rstd[i] : 1.f;
+        nm[i] = LN ? -eo.rstd[i] * eo.mean[i] : 0.f;
+    }
+    unsigned pk[2][8][2];
+    float ssum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ssq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int sl0 = g << 4;                                             // byte address of source lane 4*g
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        float b1[4], b2[4], c1[4], c2[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int sl = sl0 + ((j * 16 + r) << 2);
+            b1[r] = lane_bcast(sl, eo.cb);
+            b2[r] = lane_bcast(sl + 128, eo.cb);
+            c1[r] = LN ? lane_bcast(sl, eo.cc) : 0.f;
+            c2[r] = LN ? lane_bcast(sl + 128, eo.cc) : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float hv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float u = acc[i][j][r], v = acc[i][j + 2][r];
+                if (LN) {                                               // value = rstd * acc - rstd * mean * colsum + bias: two FMAs
+                    u = fmaf(rs[i], u, fmaf(nm[i], c1[r], b1[r]));
+                    v = fmaf(rs[i], v, fmaf(nm[i], c2[r], b2[r]));
+                } else {
+                    u += b1[r];
+                    v += b2[r];
+                }
+                hv[r] = silu_mul(u, v);
+            }
+            pk[j][i][0] = pack2(hv[0], hv[1]);
+            pk[j][i][1] = pack2(hv[2], hv[3]);
+            if (AUX) {                                                  // statistics of the ROUNDED outputs (what the next GEMM reads)
+#pragma unroll
+                for (int d = 0; d < 2; ++d) {
+                    ssum[i] = dot2_bf16(pk[j][i][d], 0x3f803f80u, ssum[i]);
+                    ssq[i] = dot2_bf16(pk[j][i][d], pk[j][i][d], ssq[i]);
+                }
+            }
+        }
+    }
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc((const __bf16*)p.C + (size_t)row0 * p.ldc + hbase);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int rrel = (2 * t + (g & 1)) * 16 + l15;
+        const bool ok = colok && row0 + rrel < p.M && !CS_ABL(p, 8);      // dbg 8: timing ablation, every store masked
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            unsigned x0 = pk[j][2 * t][0], x1 = pk[j][2 * t][1], y0 = pk[j][2 * t + 1][0], y1 = pk[j][2 * t + 1][1];
+            swap16(x0, y0);
+            swap16(x1, y1);
+            store16<CP>(u32x4{x0, x1, y0, y1}, rc, ok ? (unsigned)(rrel * p.ldc + j * 16 + 8 * (g >> 1)) * 2u : OOB);
+        }
+    }
+    if (AUX) {
+        // per-(32-hidden slice, row) partial (sum, sum of squares): slice = tn * 4 + wn; cs_ln_stats_finalize() pools the slices.
+        // Transposing reduction over the four lane rows: the half exchange adds rows g and g ^ 2 and leaves blocks b (lower half) and
+        // b + 4 (upper half), the row exchange adds the rest -- lane row g ends with the rows of blocks 2g and 2g + 1: two stores.
+        const size_t slice = (size_t)tn * 4 + wn;
+        const __amdgpu_buffer_rsrc_t rst = make_rsrc(p.stats_part + (slice * p.M + row0) * 2);
+        auto reduce = [&](const float (&v)[8], float (&out)[2]) {
+            unsigned h[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                unsigned x = __float_as_uint(v[b]), y = __float_as_uint(v[b + 4]);
+                swap32(x, y);
+                h[b] = __float_as_uint(__uint_as_float(x) + __uint_as_float(y));
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                unsigned x = h[k], y = h[k + 2];
+                swap16(x, y);
+                out[k] = __uint_as_float(x) + __uint_as_float(y);
+            }
+        };
+        float s[2], q2[2];
+        reduce(ssum, s);
+        reduce(ssq, q2);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int rrel = (2 * g + k) * 16 + l15;
+            const bool ok = colok && row0 + rrel < p.M;
+            store8<CP>(u32x2{__float_as_uint(s[k]), __float_as_uint(q2[k])}, rst, ok ? (unsigned)rrel * 8u : OOB);
         }
     }
 }
@@ -501,8 +667,9 @@ __device__ __forceinline__ void epi_resid_slab(const GemmArgs& p, const f32x16 (
 
 // store instructions one epilogue issues per wave (exact: masked lanes keep their instruction, see OOB)
 // (a count BELOW the real one would be safe -- a wait then retires more than it needs to --, one above it is not)
-template <int EPI, bool AUX, bool SLAB, int SPLIT = 0, int FM = 4>
+template <int EPI, bool AUX, bool SLAB, int SPLIT = 0, int FM = 4, int MF = 32>
 constexpr int epi_stores() {
+    if (EPI == EPI_SWIGLU_BF16 && MF == 16) return 8 + (AUX ? 2 : 0);                      // epi_swiglu_m16: the statistics leave in two stores
     if (EPI == EPI_SWIGLU_BF16) return FM * (2 + (AUX ? 1 : 0));
     if (EPI == EPI_RESID_F32) return FM * (8 + (AUX ? ((SPLIT & 2) ? 0 : 4) + 1 : 0));      // per row block: four row groups x two fp32 or two plane stores (+ the bf16 copy), + statistics
     return FM * 4;
@@ -528,8 +695,13 @@ inline bool getenv_flag(const char* name) {       // A/B switch, read at every l
 // bytes); the per-row scale of A (p.ln_rstd) and per-row scale of B (p.ln_colsum) are applied in the epilogue.
 // BMT: rows per output tile, 256 or 192 (round 4).  192 = six 32-row blocks, three per wave: launches whose 256-row tiles fill only part
 // of the chip (the student's N = 768 GEMMs at M = 12 608: 150 tiles on 256 CUs) run 198 tiles of 3/4 the work instead.
-template <int EPI, bool LN, bool AUX, bool SLAB, bool F8 = false, int SPLIT = 0, int BMT = 256>
+// MF: the bf16 MFMA of the K loop, 32 = v_mfma_f32_32x32x16_bf16 (4 x 2 blocks of 32x32 per wave), 16 = v_mfma_f32_16x16x32_bf16 (8 x 4
+// blocks of 16x16; the frozen tower's folded-LN register epilogues, see ktile_m16).  Trailing, so that the mangled names keep their head.
+template <int EPI, bool LN, bool AUX, bool SLAB, bool F8 = false, int SPLIT = 0, int BMT = 256, int MF = 32>
 __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
+    static_assert(MF == 32 || (MF == 16 && LN && !SLAB && !F8 && SPLIT == 0 && BMT == 256 && (epi_is_bf16(EPI) ? !AUX : EPI == EPI_SWIGLU_BF16)),
+                  "16x16x32 loop: the folded-LN bf16 and SwiGLU register epilogues");
+    constexpr bool M16 = MF == 16;
     static_assert(BMT == 256 || (BMT == 192 && !F8 && SPLIT == 0 && !LN && !AUX), "192-row tiles: the training schedule's plain epilogues");
     static_assert(SPLIT == 0 || (EPI == EPI_RESID_F32 && LN && !F8), "the split stream belongs to the folded-LayerNorm residual epilogue");
     static_assert(SLAB || EPI != EPI_RESID_F32, "the fp32 residual epilogue exists in the slab form only (whole-line traffic)");
@@ -542,12 +714,13 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
     constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
     constexpr int NPA = BM / 32;                 // DMA pieces of the A tile per A-loader wave (ROLES)
     constexpr int NM = FM * FN, NR = FM + FN;    // MFMAs / fragment reads per k-step and wave (8 / 6; 192-row tiles: 6 / 5)
-    constexpr int S = epi_stores<EPI, AUX, SLAB, SPLIT, FM>() < 55 ? epi_stores<EPI, AUX, SLAB, SPLIT, FM>() : 55;     // vmcnt is a 6-bit counter; fewer = safe
+    constexpr int S = epi_stores<EPI, AUX, SLAB, SPLIT, FM, MF>() < 55 ? epi_stores<EPI, AUX, SLAB, SPLIT, FM, MF>() : 55;     // vmcnt is a 6-bit counter; fewer = safe
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave - wm * WN;
-    const int hf = lane >> 5, l31 = lane & 31;
+    // a fragment read takes tile row l31 of a block and 16-byte chunk (k-step, hf): 32 rows x 2 chunks, or (MF = 16) 16 rows x 4 chunks
+    const int hf = M16 ? lane >> 4 : lane >> 5, l31 = M16 ? lane & 15 : lane & 31;
     char* const b_ring = smem + 3 * A_BYTES;
     const int ntiles = p.tiles_m * p.tiles_n, ktiles = p.K / (F8 ? 128 : BK);
     const int a_base = ((wm * TM + l31) >> 1) << 8, b_base = ((wn * TN + l31) >> 1) << 8;
@@ -700,24 +873,26 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
         int tm, tn;
         tile_of_id(p, tile, ntiles, tm, tn);
         const int row0 = tm * BM + wm * TM, colw = tn * BN + wn * TN;
-        f32x16 acc[FM][FN];
-        EpiOps eo;
-        // epilogue operands: LayerNorm statistics of the rows of the wave's four blocks (lane = row), constants of its 64 columns (lane = column)
+        f32x16 acc[M16 ? 1 : FM][M16 ? 1 : FN];
+        f32x4 acc16[M16 ? 8 : 1][M16 ? 4 : 1];
+        constexpr int RB = M16 ? 16 : 32, NRB = TM / RB;     // rows per accumulator block, row blocks per wave
+        EpiOpsT<M16 ? 8 : 4> eo;
+        // epilogue operands: LayerNorm statistics of the rows of the wave's row blocks (lane = row), constants of its 64 columns (lane = column)
         auto load_epi_ops = [&](int ln) {
-            const int l31 = ln & 31, hf = ln >> 5, lane = ln;
+            const int l31 = ln & (RB - 1), hf = ln >> 5, lane = ln;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) eo.mean[i] = eo.rstd[i] = 0.f;
+            for (int i = 0; i < (M16 ? 8 : 4); ++i) eo.mean[i] = eo.rstd[i] = 0.f;
             eo.cb = eo.cc = 0.f;
             if (LN || F8) {
 #pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    const int r = min(row0 + i * 32 + l31, p.M - 1);
+                for (int i = 0; i < NRB; ++i) {
+                    const int r = min(row0 + i * RB + l31, p.M - 1);
                     if (LN) eo.mean[i] = p.ln_mean[r];
                     eo.rstd[i] = p.ln_rstd[r];
                 }
             }
             int co;
-            if (SWI) co = hf * p.group + min(tn * 128 + wn * 32 + l31, p.group - 1);
+            if (SWI) co = hf * p.group + min(tn * 128 + wn * 32 + (lane & 31), p.group - 1);
             else co = min(colw + lane, p.N - 1);
             if (!RES) {                                    // the residual epilogue reads its column constants 8 per lane behind the slab
                 if (p.bias) eo.cb = p.bias[co];
@@ -959,7 +1134,129 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
             curA = nextA;
             gpar ^= 1;
         };
-        if constexpr (MID) {
+        // ---- MF = 16: the schedule of ktile_mid on v_mfma_f32_16x16x32_bf16.  A K tile is two 32-deep k-steps; a k-step's 8 A x 4 B fragments
+        // (one ds_read_b128 each: tile row lane & 15, chunk 4*ks + (lane >> 4)) would be 2 x 48 registers double-buffered, so a k-step runs as
+        // two HALF-STEPS of 4 A fragments x 4 B fragments = 16 MFMAs (256 matrix-pipe cycles, as one k-step of the 32x32 form), the A chunks
+        // ping-ponged and the B fragments replaced in pairs: every half-step issues its MFMAs B pair (0,1) first, so B(0,1) of the next k-step
+        // are read behind MFMA 8 of a k-step's second half and B(2,3) behind the first MFMAs of the next first half -- 48 fragment registers
+        // and 6 reads per half-step, like the 32x32 form.  Barrier between half-steps 2 and 3, A(g+2) in half-steps 1-2, B(g+2) in 3.
+        bf16x8 ga[2][M16 ? 4 : 1], gb[M16 ? 4 : 1];
+        auto ktile_m16 = [&](auto zero_tag, auto role_tag) {
+            constexpr bool ZERO = decltype(zero_tag)::value;
+            constexpr int ROLE = decltype(role_tag)::value;         // 1: B loader (waves 0-3), 2: A loader (waves 4-7)
+            const int nextA = curA == 2 ? 0 : curA + 1;
+            const char* la = smem + curA * A_BYTES + a_base;
+            const char* lb = b_ring + gpar * B_BYTES + b_base;
+            const char* la_n = smem + nextA * A_BYTES + a_base;
+            const char* lb_n = b_ring + (gpar ^ 1) * B_BYTES + b_base;
+            const int slot_a2 = curA == 0 ? 2 : curA - 1, slot_b2 = gpar;      // A(g+2) -> slot of A(g-1); B(g+2) -> slot of B(g)
+            // 16-row block blk of an operand: 8 LDS rows on, and the swizzle's bit 3 is the block's parity
+            auto frag = [&](const char* base, int ks, int blk) {
+                const int off = (((par8 | (ks * 4 + hf)) ^ sw) << 4) ^ ((blk & 1) << 7);
+                return *(const bf16x8*)(base + blk * (8 * 256) + off);
+            };
+            auto read_a = [&](const char* pa, int ks, int c) {       // A chunk c of k-step ks -> ga[c]
+#pragma unroll
+                for (int x = 0; x < 4; ++x) ga[c][x] = frag(pa, ks, c * 4 + x);
+            };
+            auto read_b = [&](const char* pb, int ks, int jj) {      // B pair jj of k-step ks
+                gb[2 * jj] = frag(pb, ks, 2 * jj);
+                gb[2 * jj + 1] = frag(pb, ks, 2 * jj + 1);
+            };
+            auto mfmas = [&](int c, int jj, bool zero) {             // 8 MFMAs: A chunk c x B pair jj
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+#pragma unroll
+                    for (int j = 2 * jj; j < 2 * jj + 2; ++j) {
+                        if (zero) {
+                            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                            acc16[c * 4 + x][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gb[j], ga[c][x], z, 0, 0, 0);
+                        } else {
+                            acc16[c * 4 + x][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gb[j], ga[c][x], acc16[c * 4 + x][j], 0, 0, 0);
+                        }
+                    }
+            };
+            // issue order of a half-step's 16 MFMAs: one LDS read behind each of MFMAs [r0a, r0a + nra) and [r0b, r0b + nrb), one DMA piece behind
+            // each of MFMAs [d0a, d0a + nda) and [d0b, d0b + ndb) -- in the program order of the reads and pieces
+            auto order = [&](auto r0a, auto nra, auto r0b, auto nrb, auto d0a, auto nda, auto d0b, auto ndb) {
+#pragma unroll
+                for (int m = 0; m < 16; ++m) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    if ((m >= r0a.value && m < r0a.value + nra.value) || (m >= r0b.value && m < r0b.value + nrb.value))
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    if ((m >= d0a.value && m < d0a.value + nda.value) || (m >= d0b.value && m < d0b.value + ndb.value))
+                        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+                }
+            };
+#define CI(N) std::integral_constant<int, (N)>{}
+            if (ZERO) {                    // first K tile of an output tile: its first fragments were not prefetched across the epilogue
+                read_a(la, 0, 0);
+                read_b(lb, 0, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+            }
+            // half-step 0 = (k-step 0, A chunk 0): B(2,3) of k-step 0, A chunk 1
+            // (the A reads go behind MFMA 8: the wait for B(2,3) in front of it is an lgkmcnt(0), it must not cover them)
+            read_b(lb, 0, 1);
+            mfmas(0, 0, ZERO);
+            read_a(la, 0, 1);
+            mfmas(0, 1, ZERO);
+            order(CI(0), CI(2), CI(8), CI(4), CI(0), CI(0), CI(0), CI(0));
+            // half-step 1 = (0, 1): A chunk 0 of k-step 1; B(0,1) of k-step 1 once their last MFMAs of k-step 0 are behind; A loaders: 4 pieces
+            read_a(la, 1, 0);
+            mfmas(1, 0, ZERO);
+            read_b(lb, 1, 0);
+            if constexpr (ROLE == 2) {
+#pragma unroll
+                for (int x = 0; x < NPA / 2; ++x) ISSUE_RA(x, slot_a2);
+            }
+            mfmas(1, 1, ZERO);
+            order(CI(0), CI(4), CI(8), CI(2), CI(10), CI(ROLE == 2 ? NPA / 2 : 0), CI(0), CI(0));
+            // half-step 2 = (1, 0): B(2,3) of k-step 1, A chunk 1; A loaders: the other 4 pieces
+            read_b(lb, 1, 1);
+            if constexpr (ROLE == 2) {
+#pragma unroll
+                for (int x = NPA / 2; x < NPA; ++x) ISSUE_RA(x, slot_a2);
+            }
+            mfmas(0, 0, false);
+            read_a(la, 1, 1);
+            mfmas(0, 1, false);
+            order(CI(0), CI(2), CI(8), CI(4), CI(2), CI(ROLE == 2 ? NPA / 2 : 0), CI(0), CI(0));
+            // K tile g+1 landed everywhere, every wave is done reading the LDS images of K tile g (the fragments of half-step 3 are in
+            // registers).  Pending ops of a B loader: B(g+1) [, the stores of an epilogue that ran since]; of an A loader: A(g+1) [, those
+            // stores], A(g+2).
+            {
+                constexpr int KEEP = ROLE == 1 ? 0 : NPA;
+                constexpr int SS = S + KEEP > 63 ? 63 - KEEP : S;
+                if (after_epi) CS_VMCNT(KEEP + SS);
+                else CS_VMCNT(KEEP);
+                after_epi = false;
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+            }
+            // half-step 3 = (1, 1): A chunk 0 and B(0,1) of K tile g+1 (past the output tile's last K tile: read, not used) and -- B loaders --
+            // the 8 pieces of B(g+2), in the order they are to issue (LDS reads and LDS-DMA writes keep their program order)
+            read_a(la_n, 0, 0);
+            if constexpr (ROLE == 1) { ISSUE_RB(0, slot_b2); ISSUE_RB(1, slot_b2); ISSUE_RB(2, slot_b2); ISSUE_RB(3, slot_b2); }
+            mfmas(1, 0, false);
+            read_b(lb_n, 0, 0);
+            if constexpr (ROLE == 1) { ISSUE_RB(4, slot_b2); ISSUE_RB(5, slot_b2); ISSUE_RB(6, slot_b2); ISSUE_RB(7, slot_b2); }
+            mfmas(1, 1, false);
+            order(CI(0), CI(4), CI(8), CI(2), CI(4), CI(ROLE == 1 ? 4 : 0), CI(10), CI(ROLE == 1 ? 4 : 0));
+#undef CI
+            if (ROLE == 1) adv_b();
+            else adv_a();
+            curA = nextA;
+            gpar ^= 1;
+        };
+        if constexpr (M16) {
+            if (role_a) {
+                ktile_m16(std::true_type{}, std::integral_constant<int, 2>{});
+                for (int kt = 1; kt < ktiles; ++kt) ktile_m16(std::false_type{}, std::integral_constant<int, 2>{});
+            } else {
+                ktile_m16(std::true_type{}, std::integral_constant<int, 1>{});
+                for (int kt = 1; kt < ktiles; ++kt) ktile_m16(std::false_type{}, std::integral_constant<int, 1>{});
+            }
+        } else if constexpr (MID) {
             if (role_a) {
                 ktile_mid(std::true_type{}, std::integral_constant<int, 2>{});
                 for (int kt = 1; kt < ktiles; ++kt) ktile_mid(std::false_type{}, std::integral_constant<int, 2>{});
@@ -1022,7 +1319,9 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
             }
         } else {
             load_epi_ops(lane_e);
-            if constexpr (SWI) epi_swiglu<LN, AUX, CP, FM>(p, acc, lane_e, row0, tn, wn, eo);
+            if constexpr (M16 && SWI) epi_swiglu_m16<LN, AUX, CP>(p, acc16, lane_e, row0, tn, wn, eo);
+            else if constexpr (M16) epi_bf16_m16<epi_act(EPI), LN, CP>(p, acc16, lane_e, row0, colw, eo);
+            else if constexpr (SWI) epi_swiglu<LN, AUX, CP, FM>(p, acc, lane_e, row0, tn, wn, eo);
             else epi_bf16<epi_act(EPI), LN, CP, F8, FM>(p, acc, lane_e, row0, colw, eo);
         }
     }
@@ -1033,12 +1332,12 @@ __global__ __launch_bounds__(512) void gemm_stream_kernel(GemmArgs p) {
 #undef ISSUE_RB
 }
 
-template <int EPI, bool LN, bool AUX, bool SLAB, int BMT = 256>
+template <int EPI, bool LN, bool AUX, bool SLAB, int BMT = 256, int MF = 32>
 int launch_stream_v(const GemmArgs& a, unsigned grid, hipStream_t stream) {
     constexpr size_t lds = 160 * 1024;
-    static bool once = ((void)hipFuncSetAttribute((const void*)gemm_stream_kernel<EPI, LN, AUX, SLAB, false, 0, BMT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
+    static bool once = ((void)hipFuncSetAttribute((const void*)gemm_stream_kernel<EPI, LN, AUX, SLAB, false, 0, BMT, MF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
     (void)once;
-    hipLaunchKernelGGL((gemm_stream_kernel<EPI, LN, AUX, SLAB, false, 0, BMT>), dim3(grid), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((gemm_stream_kernel<EPI, LN, AUX, SLAB, false, 0, BMT, MF>), dim3(grid), dim3(512), lds, stream, a);
     CS_LAUNCH_CHECK();
     return 0;
 }
@@ -1048,7 +1347,12 @@ int launch_stream_v(const GemmArgs& a, unsigned grid, hipStream_t stream) {
 template <int EPI, bool LN, bool AUX>
 int launch_stream_t(const GemmArgs& a, unsigned grid, hipStream_t stream) {
     if constexpr (EPI == EPI_RESID_F32) return launch_stream_v<EPI, LN, AUX, true>(a, grid, stream);
-    else return (a.dbg & 1) ? launch_stream_v<EPI, LN, AUX, true>(a, grid, stream) : launch_stream_v<EPI, LN, AUX, false>(a, grid, stream);
+    else if (a.dbg & 1) return launch_stream_v<EPI, LN, AUX, true>(a, grid, stream);
+    // the frozen tower's folded-LN launches (q|k|v, W1|W2; QuickGELU c_fc) run the K loop on the 16x16x32 MFMA; CS_GEMM_MFMA32=1: the 32x32x16 loop (A/B switch)
+    else if constexpr (LN && (epi_is_bf16(EPI) ? !AUX : EPI == EPI_SWIGLU_BF16)) {
+        if (!getenv_flag("CS_GEMM_MFMA32")) return launch_stream_v<EPI, LN, AUX, false, 256, 16>(a, grid, stream);
+        return launch_stream_v<EPI, LN, AUX, false>(a, grid, stream);
+    } else return launch_stream_v<EPI, LN, AUX, false>(a, grid, stream);
 }
 
 template <bool AUX, int SPLIT>

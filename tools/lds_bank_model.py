@@ -70,6 +70,17 @@ for t in range(7):
     for ks in range(4):
         tot+=cycles(kread(t,ks),G128,4,64);n+=1
 print("K frag read cycles avg",tot/n)
+# the same operand image read for v_mfma_f32_16x16x32_bf16 (gemm_stream.hip, MF = 16): tile row blk*16 + (l & 15), 16-byte chunk 4*ks + (l >> 4)
+def m16read(blk,ks):
+    def f(l):
+        row=blk*16+(l&15); ch=4*ks+(l>>4)
+        return ((row>>1)<<8)+((((row&1)<<3)|ch)^((row>>1)&15))*16
+    return f
+tot=0;n=0;worst=0
+for blk in range(8):
+    for ks in range(2):
+        c=cycles(m16read(blk,ks),G128,4,64); worst=max(worst,c); tot+=c;n+=1
+print("16x16x32 frag read cycles avg",tot/n,"worst",worst,"(ideal 4)")
 # K writes (ds_write_b128): thread idx -> row idx>>3, chunk idx&7
 def kwrite(wave,it,NT):
     def f(l):
