@@ -66,7 +66,7 @@ SIGNATURES = {
     "cs_colsum_bf16": (_i, [_vp, _l, _vp, _vp, _i, _i, _vp]),
     "cs_im2row": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "cs_cls_row": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "cs_roialign_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "cs_roialign_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _f, _vp, _l, _vp, _vp, _l, _vp]),
     "cs_roialign_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "cs_cosine_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "cs_cosine_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp]),
@@ -143,6 +143,7 @@ class HipOps:
     ATTN_NO_ROPE = True                 # attn_fwd / attn_fwd_stats / attn_cls_fwd / attn_bwd(cos=None, sin=None): no rotary embedding, any Ntok > 1
     TOKEN_TAPS = True                   # tokens_to_nchw: the residual stream after a block as a [B, C, h, w] map (encode_dense(taps=), the detector backbone)
     DECONV_ROWS = True                  # rows_to_nchw / nchw_to_rows: 2x2 transposed convolutions as GEMMs on token rows (neck.Deconv2x2)
+    BOX_SCORES = True                   # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
         self.lib = load_library()
@@ -674,11 +675,48 @@ class HipOps:
         B, Ntok, C = x.shape
         self._ok(self.lib.cs_cls_row(_p(x), _p(cls), _p(pos), B, Ntok, C, self._stream()), "cs_cls_row")
 
-    def roialign_fwd(self, feat, rois, pooled, grid_h, grid_w, tok_off):
+    @staticmethod
+    def _token_map(feat, grid_h, grid_w, tok_off):
+        """-> (B, Ntok, E) of a token-major fp32 map: [B, Ntok, E], or its grid as a [B, h, w, E] view with strides (Ntok*E, w*E, E, 1)."""
+        E = feat.shape[-1]
+        assert feat.dtype == torch.float32 and feat.stride(-1) == 1 and E % 4 == 0 and feat.stride(0) % E == 0 and feat.data_ptr() % 16 == 0
+        if feat.dim() == 4:
+            assert tuple(feat.shape[1:3]) == (grid_h, grid_w) and feat.stride(2) == E and feat.stride(1) == grid_w * E, \
+                "a [B, h, w, E] map must be a view of the token-major layout"
+        else:
+            assert feat.dim() == 3 and feat.stride(1) == E
+        Ntok = feat.stride(0) // E if feat.shape[0] > 1 else max(feat.stride(0) // E, tok_off + grid_h * grid_w)
+        return feat.shape[0], Ntok, E
+
+    def roialign_fwd(self, feat, rois, pooled, grid_h, grid_w, tok_off, *, box_scale=0.0):
+        """box_scale = 0: boxes normalised to [0, 1], unchecked (the distillation path).  box_scale = 1 / featmap_stride: pixel boxes,
+        torchvision's scaling; image indices outside the map and boxes wider than twice the grid pool to 0 (include/clipself_hip.h)."""
         self._chk(feat, rois, pooled)
-        B, Ntok, E = feat.shape
-        self._ok(self.lib.cs_roialign_fwd(_p(feat), _p(rois), _p(pooled), rois.shape[0], Ntok, grid_h, grid_w, E, tok_off,
-                                          self._stream()), "cs_roialign_fwd")
+        B, Ntok, E = self._token_map(feat, grid_h, grid_w, tok_off)
+        assert rois.is_contiguous() and rois.dtype == torch.float32 and pooled.is_contiguous() and pooled.dtype == torch.float32
+        self._ok(self.lib.cs_roialign_fwd(_p(feat), _p(rois), _p(pooled), rois.shape[0], Ntok, grid_h, grid_w, E, tok_off, float(box_scale),
+                                          B if box_scale else 0, None, 0, 0.0, None, 0, None, None, 0, self._stream()), "cs_roialign_fwd")
+
+    def box_scores(self, feat, rois, class_embed, scores, grid_h, grid_w, tok_off, box_scale, vlm_temp, det_logits=None, expo=None, pooled=None):
+        """Open-vocabulary box scores in one launch (cs_roialign_fwd's scoring form): pool every pixel box of rois [K, 5] from the
+        token-major map, normalise, take logits against class_embed [C, E] (fp32, contiguous) times vlm_temp, softmax, and blend with
+        softmax(det_logits [K, C]) by the per-class exponents expo [C]:  scores = det^(1-expo) * vlm^expo, evaluated in the log domain;
+        det_logits None -> the VLM softmax alone.  pooled [K, E] (optional) receives the pooled features, not normalised."""
+        self._chk(feat, rois, class_embed, scores, det_logits, expo, pooled)
+        B, Ntok, E = self._token_map(feat, grid_h, grid_w, tok_off)
+        K, C = rois.shape[0], class_embed.shape[0]
+        f32 = torch.float32
+        assert rois.is_contiguous() and rois.dtype == f32 and tuple(rois.shape) == (K, 5)
+        assert class_embed.is_contiguous() and class_embed.dtype == f32 and class_embed.shape[1] == E and class_embed.data_ptr() % 16 == 0
+        assert scores.dtype == f32 and tuple(scores.shape) == (K, C) and scores.stride(1) == 1
+        assert det_logits is None or (det_logits.dtype == f32 and tuple(det_logits.shape) == (K, C) and det_logits.stride(1) == 1)
+        assert det_logits is None or (expo is not None and expo.dtype == f32 and expo.is_contiguous() and expo.numel() == C), \
+            "det_logits needs the per-class exponents"
+        assert pooled is None or (pooled.is_contiguous() and pooled.dtype == f32 and tuple(pooled.shape) == (K, E))
+        self._ok(self.lib.cs_roialign_fwd(_p(feat), _p(rois), _p(pooled), K, Ntok, grid_h, grid_w, E, tok_off, float(box_scale), B,
+                                          _p(class_embed), C, float(vlm_temp), _p(det_logits), det_logits.stride(0) if det_logits is not None else 0,
+                                          _p(expo) if det_logits is not None else None, _p(scores), scores.stride(0), self._stream()),
+                 "cs_roialign_fwd")
 
     def roialign_bwd(self, dpooled, rois, dfeat, grid_h, grid_w, tok_off):
         self._chk(dpooled, rois, dfeat)

@@ -266,9 +266,27 @@ int cs_im2row(const void* img, int img_dtype, void* out, int B, int S, int p, in
 int cs_cls_row(float* x, const float* cls, const float* pos, int B, int Ntok, int C, cs_stream_t stream);      /* x[b,0,:] = cls + pos[0], :540-543 */
 
 /* --- RoIAlign 1x1 / aligned / adaptive sampling on the token-major map: torchvision.ops.roi_align called at
- *     eva_vit_model.py:628-629 with boxes from _denormalize_boxes :655-664 (boxes given normalised to [0,1]). */
+ *     eva_vit_model.py:628-629 with boxes from _denormalize_boxes :655-664 (boxes given normalised to [0,1]).
+ *     feat [B, Ntok, E] f32, the grid in tokens tok_off .. tok_off + grid_h*grid_w - 1; rois [K,5] f32 = (image, x0, y0, x1, y1);
+ *     pooled [K, E] f32; E % 4 == 0, grid sides <= 128, K >= 0.
+ * Trailing arguments (F-ViT/models/fvit_head.py:63-70,108-119,267-277: the detector's open-vocabulary scoring tail):
+ *   box_scale   0 = boxes normalised to [0,1], map coordinate = roi * (grid_w, grid_h) - 0.5.  Otherwise pixel boxes and
+ *               map coordinate = __fmul_rn(roi, box_scale) - 0.5 with box_scale = 1 / featmap_stride: torchvision's spatial_scale.
+ *   B           image count for the index check, 0 = unchecked.
+ *   class_embed [C, E] f32 row-major, 16-byte aligned, or NULL.  Given, the launch also writes
+ *                 v^ = v / max(|v|_2, 1e-12);  z_c = vlm_temp * <v^, class_embed[c]>;  lv = z - logsumexp(z)
+ *                 scores[k*lds + c] = exp(lv_c)                                              det_logits == NULL
+ *                 scores[k*lds + c] = exp((1 - expo[c]) * ld_c + expo[c] * lv_c)             ld = log_softmax(det_logits[k*ldd .. + C))
+ *               i.e. softmax(det)^(1-expo) * softmax(z)^expo in the log domain.  fp32 operands and accumulation throughout, no atomics,
+ *               fixed summation order (equal inputs, equal bits), no workspace.  pooled may then be NULL; given, it receives v.
+ *   With class_embed == NULL, box_scale == 0 and B == 0 the launch is the plain pooling kernel, boxes unchecked.  In every other form
+ *   boxes are BOUNDED: one whose image index is outside [0, B) (B > 0), or whose extent on the map is not in (0, 2 * grid side] on both
+ *   axes -- non-finite coordinates included -- is an empty box: v = 0, hence a uniform softmax(z); the map is never indexed by it.
+ *   Returns -1 (cs_last_error) without launching for C < 1, ldd < C, lds < C, scores == NULL, det_logits without expo, det_logits or
+ *   scores without class_embed, pooled == NULL without class_embed, or E + C past one workgroup's LDS (E + C <= 40000 fits). */
 int cs_roialign_fwd(const float* feat, const float* rois, float* pooled, int K, int Ntok, int grid_h, int grid_w, int E,
-                    int tok_off, cs_stream_t stream);
+                    int tok_off, float box_scale, int B, const float* class_embed, int C, float vlm_temp, const float* det_logits,
+                    long ldd, const float* expo, float* scores, long lds, cs_stream_t stream);
 /* backward: dfeat [B, Ntok, E] += the boxes' gradients; a gather per map cell over the image's boxes in ascending box order (no atomics:
  * bit-reproducible, unlike torchvision's atomicAdd scatter); any E: 1024 channels per workgroup, wider maps take more workgroups) */
 int cs_roialign_bwd(const float* dpooled, const float* rois, float* dfeat, int K, int B, int Ntok, int grid_h, int grid_w, int E,
