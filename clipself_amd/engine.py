@@ -23,7 +23,10 @@ Memory layout (MI355X: 288 GB HBM3E -- nothing is recomputed, nothing is re-laid
   * residual stream fp32 [B*N, C]; every GEMM operand bf16; LayerNorm / softmax statistics fp32.
 
 The flat store, the trainable flags, the fold guard and the tower-level drivers (encode_image, encode_dense, backward_dense, AdamW) are
-family-neutral and live in engine_base.TowerEngine; this module holds what names EVA02 parameters: layout, stem, blocks, head, fp8 operands.
+family-neutral and live in engine_base.TowerEngine, and so does the schedule code both families share (the CLS-only last block, the q|k|v
+head of the folded teacher block, the head of the backward pass); this module holds what names EVA02 parameters: layout, stem, blocks, head,
+fp8 operands.  The stacked matrices are read through one accessor (`_stacked`), a block's four linears are listed once (`_block_linears`),
+and the block behind the attention core is written once (`_block_tail`).
 
 The engine is backend-agnostic on purpose: `ops` is clipself_amd.hip.HipOps in the product; the CPU test-suite
 injects the per-kernel references (oracle/ops_ref.py) to verify this schedule -- in particular the hand-written
@@ -31,6 +34,7 @@ backward -- against the monolithic autograd oracle without a GPU.  The product n
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -48,12 +52,12 @@ def param_groups_layout(cfg: TowerCfg, prefix: str = "visual."):
     that every GEMM sees K % 64 == 0 and 16-byte rows (EVA02-L/14: hidden 2730 -> 2752, 3*14*14 = 588 -> 640; for
     B/16 both are already multiples of 64 and storage == logical).  Names containing '._' are private padding."""
     C, Hd, E, p = cfg.width, cfg.hidden, cfg.embed_dim, cfg.patch_size
-    Hp, Kpe, Kp = padded_hidden(cfg), 3 * p * p, _round_up(3 * p * p, 64)
+    Hp, Kp = padded_hidden(cfg), _round_up(3 * p * p, 64)
     t = lambda name, shape, storage=None: (name, shape, storage if storage is not None else shape)
     groups = [[t(prefix + "cls_token", (1, 1, C))], [t(prefix + "pos_embed", (1, cfg.tokens, C))],
               [t(prefix + "patch_embed.proj.weight", (C, 3, p, p), (C, Kp))], [t(prefix + "patch_embed.proj.bias", (C,))]]
     for i in range(cfg.layers):
-        b = f"{prefix}blocks.{i}."
+        b = f"{prefix}{EvaEngine.BLOCK_TAG}{i}."
         groups += [
             [t(b + "norm1.weight", (C,))], [t(b + "norm1.bias", (C,))],
             [t(b + "attn.q_proj.weight", (C, C)), t(b + "attn.k_proj.weight", (C, C)), t(b + "attn.v_proj.weight", (C, C))],
@@ -72,7 +76,8 @@ def param_groups_layout(cfg: TowerCfg, prefix: str = "visual."):
 
 
 class EvaEngine(TowerEngine):
-    BLOCK_TAG, FINAL_NORM, RESID_BIAS = "blocks.", "norm", "mlp.w3.bias"
+    BLOCK_TAG, NORM1, FINAL_NORM, RESID_BIAS = "blocks.", "norm1", "norm", "mlp.w3.bias"
+    STACKED = {"attn.q_proj.weight": 3, "attn.q_bias": 3, "mlp.w1.weight": 2, "mlp.w1.bias": 2}      # first tensor of a stacked group: tensors in it (_stacked)
     FP8_MAX_ROW = 8192                        # widest row cs_quant_rows_fp8 quantises (one row per wave, held in registers)
 
     def _layout(self):
@@ -91,7 +96,7 @@ class EvaEngine(TowerEngine):
         super().__init__(cfg, ops, trainable=trainable, prefix=prefix)
         # Frozen towers fold the two sub-LayerNorms (inner_attn_ln ahead of proj, ffn_ln ahead of w3) into the following GEMM:
         # gamma goes into a bf16 copy of the weight, beta and the row statistics into the GEMM epilogue, and the statistics
-        # come out of the producing kernels' epilogues -- the LN passes over [M,C] and [M,hidden] disappear (_block_post_folded).
+        # come out of the producing kernels' epilogues -- the LN passes over [M,C] and [M,hidden] disappear (_block_tail_folded).
         # fold_block_ln (norm1 / norm2 into the q|k|v and W1|W2 GEMMs, behind the guard) builds on it; the sub-LayerNorm folds themselves
         # are never worse than the plain schedule (their input is a stored bf16 tensor either way) and need no guard.
         self.fold_sub_ln = not trainable
@@ -150,7 +155,7 @@ class EvaEngine(TowerEngine):
         self.fold = {}
         with torch.no_grad():
             for i in range(cfg.layers):
-                b = f"{self.prefix}blocks.{i}."
+                b = self._b(i)
                 out = {}
                 for key, wname, ln, bname, K in (("proj", "attn.proj.weight", "attn.inner_attn_ln", "attn.proj.bias", C),
                                                  ("w3", "mlp.w3.weight", "mlp.ffn_ln", "mlp.w3.bias", Hl)):
@@ -161,11 +166,9 @@ class EvaEngine(TowerEngine):
                     out[key] = (Wf, Wf.float().sum(dim=1).contiguous(), (W[:, :K] @ beta + self.p[b + bname]).contiguous())
                 if self.fold_block_ln:
                     # norm1 -> [Wq;Wk;Wv] and norm2 -> [W1;W2]: the stacked matrices and biases are adjacent in the flat store
-                    Hd = self.Hp
-                    for key, wname, bias_name, ln, rows in (("qkv", "attn.q_proj.weight", "attn.q_bias", "norm1", 3 * C),
-                                                           ("w12", "mlp.w1.weight", "mlp.w1.bias", "norm2", 2 * Hd)):
-                        o, ob = self.offsets[b + wname][0], self.offsets[b + bias_name][0]
-                        W, bias = self.master[o:o + rows * C].view(rows, C), self.master[ob:ob + rows]
+                    for key, wname, bias_name, ln in (("qkv", "attn.q_proj.weight", "attn.q_bias", "norm1"),
+                                                     ("w12", "mlp.w1.weight", "mlp.w1.bias", "norm2")):
+                        W, bias = self._stacked(self.master, wname, i), self._stacked(self.master, bias_name, i)
                         g, beta = self.p[b + ln + ".weight"], self.p[b + ln + ".bias"]
                         Wf = (W * g[None, :]).to(BF16).contiguous()
                         out[key] = (Wf, Wf.float().sum(dim=1).contiguous(), (W @ beta + bias).contiguous())
@@ -173,17 +176,8 @@ class EvaEngine(TowerEngine):
 
     def sync_transposed(self, blocks=None):
         """W^T shadows for the dgrad GEMMs (dx = dy . W needs W with the contraction dimension contiguous)."""
-        cfg, C, Hd = self.cfg, self.cfg.width, self.Hp
-        pairs = []
-        for i in (range(self.first_trainable, cfg.layers) if blocks is None else blocks):
-            b = f"{self.prefix}blocks.{i}."
-            o = self.offsets[b + "attn.q_proj.weight"][0]
-            pairs.append((self.shadow[o:o + 3 * C * C].view(3 * C, C), self._wt_alloc((i, "qkv"), 3 * C, C)))
-            pairs.append((self.w[b + "attn.proj.weight"], self._wt_alloc((i, "proj"), C, C)))
-            o = self.offsets[b + "mlp.w1.weight"][0]
-            pairs.append((self.shadow[o:o + 2 * Hd * C].view(2 * Hd, C), self._wt_alloc((i, "w12"), 2 * Hd, C)))
-            pairs.append((self.storage_of(self.shadow, b + "mlp.w3.weight"), self._wt_alloc((i, "w3"), C, Hd)))
-        pairs.append((self.w[self.prefix + "head.weight"], self._wt_alloc("head", self.cfg.embed_dim, C)))
+        pairs = self._block_wt_pairs(blocks)
+        pairs.append((self.w[self.prefix + "head.weight"], self._wt_alloc("head", self.cfg.embed_dim, self.cfg.width)))
         self.ops.transpose_bf16_batched(pairs)          # one launch (49 matrices per step for B/16)
 
     # ------------------------------------------------------------------------------------------ fp8 forward operands
@@ -197,18 +191,13 @@ class EvaEngine(TowerEngine):
 
     def sync_fp8(self, blocks=None):
         """e4m3 shadows (+ per-output-row scales) of the four weight matrices of every block, from the bf16 shadows."""
-        cfg, C, Hd = self.cfg, self.cfg.width, self.Hp
-        for i in (range(cfg.layers) if blocks is None else blocks):
-            b = f"{self.prefix}blocks.{i}."
-            o = self.offsets[b + "attn.q_proj.weight"][0]
-            self.w8[(i, "qkv")] = self._fp8_rows(self.shadow[o:o + 3 * C * C].view(3 * C, C))
-            self.w8[(i, "proj")] = self._fp8_rows(self.w[b + "attn.proj.weight"])
-            o = self.offsets[b + "mlp.w1.weight"][0]
-            self.w8[(i, "w12")] = self._fp8_rows(self.shadow[o:o + 2 * Hd * C].view(2 * Hd, C))
-            self.w8[(i, "w3")] = self._fp8_rows(self.storage_of(self.shadow, b + "mlp.w3.weight"))
+        for i in (range(self.cfg.layers) if blocks is None else blocks):
+            linears = self._block_linears(i)
+            for key, W in linears:
+                self.w8[(i, key)] = self._fp8_rows(W)
             if self.fp8_dgrad and i >= self.first_trainable:
-                for key, n in (("qkv", 3 * C), ("proj", C), ("w12", 2 * Hd), ("w3", C)):
-                    self.wt8[(i, key)] = self._fp8_rows(self.wt[(i, key)][:, :n])
+                for key, W in linears:                     # ... and of their W^T shadows (the columns past W's row count are padding)
+                    self.wt8[(i, key)] = self._fp8_rows(self.wt[(i, key)][:, :W.shape[0]])
 
     def _dgrad(self, i, key, dY, out, cols=None, q=None):
         """out (bf16) = dY . W for the linear `key` of block i, through the transposed shadow (contraction over the output features, or over
@@ -306,32 +295,37 @@ class EvaEngine(TowerEngine):
             keep["patches"] = A                  # operand of the patch-embedding weight gradient
         return x, g
 
-    def _qkv_w(self, b):
-        C = self.cfg.width
-        o = self.offsets[b + "attn.q_proj.weight"][0]
-        ob = self.offsets[b + "attn.q_bias"][0]
-        return self.shadow[o:o + 3 * C * C].view(3 * C, C), self.master[ob:ob + 3 * C]
+    def _stacked(self, buf, name, i):
+        """A stacked group of block i inside a flat buffer (master, shadow, grad) as ONE matrix / vector -- [Wq;Wk;Wv] [3C, C],
+        [q_bias;0;v_bias] [3C], [W1;W2] [2 Hp, C], [b1;b2] [2 Hp] --, named by its first tensor: the group's tensors have one storage shape
+        and are adjacent in the flat store (param_groups_layout)."""
+        o, st = self.offsets[self._b(i) + name]
+        n = self.STACKED[name]
+        return buf[o:o + n * math.prod(st)].view(n * st[0], *st[1:])
 
-    def _w12(self, b):
-        C, Hd = self.cfg.width, self.Hp
-        o = self.offsets[b + "mlp.w1.weight"][0]
-        ob = self.offsets[b + "mlp.w1.bias"][0]
-        return self.shadow[o:o + 2 * Hd * C].view(2 * Hd, C), self.master[ob:ob + 2 * Hd]
+    def _qkv_operands(self, i):
+        return self._stacked(self.shadow, "attn.q_proj.weight", i), self._stacked(self.master, "attn.q_bias", i)
+
+    def _w12(self, i):
+        return self._stacked(self.shadow, "mlp.w1.weight", i), self._stacked(self.master, "mlp.w1.bias", i)
+
+    def _block_linears(self, i):
+        b = self._b(i)
+        return (("qkv", self._stacked(self.shadow, "attn.q_proj.weight", i)), ("proj", self.w[b + "attn.proj.weight"]),
+                ("w12", self._stacked(self.shadow, "mlp.w1.weight", i)), ("w3", self.storage_of(self.shadow, b + "mlp.w3.weight")))
 
     def _block_fwd(self, i, x, B, N, cos, sin, with_attn=True, save=None, inplace=True):
         """x: fp32 [B*N, C].  Returns the block output (x itself when inplace)."""
         ops, cfg = self.ops, self.cfg
-        C, Hd, Hl, H, eps = cfg.width, self.Hp, cfg.hidden, cfg.heads, cfg.ln_eps      # Hd: padded storage width, Hl: logical
-        padded = Hd != Hl
-        b = f"{self.prefix}blocks.{i}."
+        C, H, eps = cfg.width, cfg.heads, cfg.ln_eps
+        b = self._b(i)
         M = B * N
         keep = save is not None
-        st = (lambda: (ops.empty((M,), F32), ops.empty((M,), F32))) if keep else (lambda: (None, None))
 
         ln1 = ops.empty((M, C), BF16)
-        m1, r1 = st()
+        m1, r1 = self._row_stats(M, keep)
         q1 = self._ln(x, self.p[b + "norm1.weight"], self.p[b + "norm1.bias"], ln1, m1, r1, eps)
-        wqkv, bqkv = self._qkv_w(b)
+        wqkv, bqkv = self._qkv_operands(i)
         qkv = lse = None
         if with_attn and not keep and inplace and self.fold_sub_ln:
             qkv = ops.empty((M, 3 * C), BF16)
@@ -339,7 +333,7 @@ class EvaEngine(TowerEngine):
             att = ops.empty((M, C), BF16)
             part = ops.empty((H, M, 2), F32)
             ops.attn_fwd_stats(qkv, cos, sin, att, None, part, B, N, H, cfg.head_width ** -0.5)
-            return self._block_post_folded(i, b, x, att, part, M)
+            return self._block_tail_folded(i, x, att, part)
         if with_attn:
             qkv = ops.empty((M, 3 * C), BF16)
             self._linear(i, "qkv", ln1, wqkv, qkv, bqkv, xq=q1)
@@ -349,27 +343,28 @@ class EvaEngine(TowerEngine):
         else:
             att = ops.empty((M, C), BF16)      # v only: every token "attends" to itself (proj_without_attn)
             self._linear(i, "qkv", ln1, wqkv[2 * C:], att, bqkv[2 * C:], rows=(2 * C, 3 * C), xq=q1)
-        x2 = self._block_post(i, b, x, att, M, st, save, inplace)
+        x2 = self._block_tail(i, x, att, save, inplace)
         if keep:
             save.update(x0=x, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, att=att, with_attn=with_attn)
         return x2
 
-    def _block_post(self, i, b, x, att, M, st, save, inplace):
-        """Everything after the attention core: inner_attn_ln -> proj (+x) -> norm2 -> SwiGLU -> ffn_ln -> w3 (+x1)."""
+    def _block_tail(self, i, x, att, save=None, inplace=True):
+        """Everything after the attention core, for whichever rows x fp32 [M, C] / att bf16 [M, C] hold: inner_attn_ln -> proj (+x) -> norm2 ->
+        SwiGLU -> ffn_ln -> w3 (+x1).  inplace: x1 and x2 are x itself; save (dict): what _block_bwd needs is kept and put into it."""
         ops, cfg = self.ops, self.cfg
-        C, Hd, Hl, eps = cfg.width, self.Hp, cfg.hidden, cfg.ln_eps
-        padded = Hd != Hl
+        C, Hd, Hl, eps = cfg.width, self.Hp, cfg.hidden, cfg.ln_eps      # Hd: padded storage width, Hl: logical
+        b, M = self._b(i), x.shape[0]
         keep = save is not None
         iln = ops.empty((M, C), BF16)
-        m2, r2 = st()
+        m2, r2 = self._row_stats(M, keep)
         q2 = self._ln(att, self.p[b + "attn.inner_attn_ln.weight"], self.p[b + "attn.inner_attn_ln.bias"], iln, m2, r2, eps)
         x1 = x if inplace else ops.empty((M, C), F32)
         self._linear(i, "proj", iln, self.w[b + "attn.proj.weight"], x1, self.p[b + "attn.proj.bias"], extra=x, epi=EPI_RESID_F32, xq=q2)
 
         ln2 = ops.empty((M, C), BF16)
-        m3, r3 = st()
+        m3, r3 = self._row_stats(M, keep)
         q3 = self._ln(x1, self.p[b + "norm2.weight"], self.p[b + "norm2.bias"], ln2, m3, r3, eps)
-        w12, b12 = self._w12(b)
+        w12, b12 = self._w12(i)
         hid = ops.empty((M, Hd), BF16)
         x12 = None
         if keep or self.fp8_forward:
@@ -380,8 +375,8 @@ class EvaEngine(TowerEngine):
             ops.swiglu_fwd(x12, hid)
         else:
             ops.gemm_nt(ln2, w12, hid, bias=b12, epi=EPI_SWIGLU_BF16, group=Hd)
-        fln = (ops.zeros if padded else ops.empty)((M, Hd), BF16)     # padding columns feed the W3 GEMM: must be exact zeros
-        m4, r4 = st()
+        fln = (ops.zeros if Hd != Hl else ops.empty)((M, Hd), BF16)   # padding columns feed the W3 GEMM: must be exact zeros
+        m4, r4 = self._row_stats(M, keep)
         q4 = self._ln(hid[:, :Hl], self.p[b + "mlp.ffn_ln.weight"], self.p[b + "mlp.ffn_ln.bias"], fln[:, :Hl], m4, r4, eps)
         x2 = x1 if inplace else ops.empty((M, C), F32)
         self._linear(i, "w3", fln, self.storage_of(self.shadow, b + "mlp.w3.weight"), x2, self.p[b + "mlp.w3.bias"], extra=x1,
@@ -390,10 +385,11 @@ class EvaEngine(TowerEngine):
             save.update(iln=iln, st2=(m2, r2), x1=x1, ln2=ln2, st3=(m3, r3), x12=x12, hid=hid, fln=fln, st4=(m4, r4))
         return x2
 
-    def _block_post_folded(self, i, b, x, att, att_part, M):
-        """_block_post for a frozen tower with both sub-LayerNorms folded into proj / w3 (in place on x)."""
+    def _block_tail_folded(self, i, x, att, att_part):
+        """_block_tail for a frozen tower with both sub-LayerNorms folded into proj / w3 (in place on x)."""
         ops, cfg = self.ops, self.cfg
         C, Hd, Hl, eps = cfg.width, self.Hp, cfg.hidden, cfg.ln_eps
+        b, M = self._b(i), x.shape[0]
         f = self.fold[i]
         mean, rstd = ops.empty((M,), F32), ops.empty((M,), F32)
         ops.ln_stats_finalize(att_part, 64, C, mean, rstd, eps)
@@ -402,7 +398,7 @@ class EvaEngine(TowerEngine):
 
         ln2 = ops.empty((M, C), BF16)
         ops.layernorm_fwd(x, self.p[b + "norm2.weight"], self.p[b + "norm2.bias"], ln2, None, None, eps)
-        w12, b12 = self._w12(b)
+        w12, b12 = self._w12(i)
         hid = ops.empty((M, Hd), BF16)
         part = ops.empty((4 * ((Hd + 127) // 128), M, 2), F32)
         ops.gemm_nt_ln(ln2, w12, hid, bias=b12, stats_part=part, epi=EPI_SWIGLU_BF16, group=Hd)
@@ -418,19 +414,10 @@ class EvaEngine(TowerEngine):
         tower, which reads fp32 x, and the last one (emit_next False), which writes fp32 x again (cs_gemm_nt_ln_split)."""
         ops, cfg = self.ops, self.cfg
         C, Hd, Hl, H, eps = cfg.width, self.Hp, cfg.hidden, cfg.heads, cfg.ln_eps
-        b = f"{self.prefix}blocks.{i}."
         M = B * N
         f = self.fold[i]
-        qkv = ops.empty((M, 3 * C), BF16)
         first = xb is None
-        if first:
-            ln1 = ops.empty((M, C), BF16)
-            ops.layernorm_fwd(x, self.p[b + "norm1.weight"], self.p[b + "norm1.bias"], ln1, None, None, eps)
-            wqkv, bqkv = self._qkv_w(b)
-            ops.gemm_nt(ln1, wqkv, qkv, bias=bqkv, epi=EPI_BF16)
-        else:
-            Wq, cq, dq = f["qkv"]
-            ops.gemm_nt_ln(xb, Wq, qkv, bias=dq, ln_mean=st[0], ln_rstd=st[1], ln_colsum=cq, epi=EPI_BF16)
+        qkv = self._teacher_qkv(i, x, xb, st, M)
         att = ops.empty((M, C), BF16)
         part_a = ops.empty((H, M, 2), F32)
         ops.attn_fwd_stats(qkv, cos, sin, att, None, part_a, B, N, H, cfg.head_width ** -0.5)
@@ -455,38 +442,6 @@ class EvaEngine(TowerEngine):
         ops.ln_stats_finalize(part_x, 64, C, mean2, rstd2, eps)
         return xb2, (mean2, rstd2)
 
-    def _block_fwd_cls(self, i, x, B, N, cos, sin, xb=None, st=None, lo=None):
-        """Last teacher block restricted to what encode_image() consumes: the CLS row.  x fp32 [B*N, C] -> fp32 [B, C].
-        forward_features() returns x[:, 0] after the final norm (eva_vit_model.py:505-519), so only the CLS *query* of the
-        last block is live; keys and values still come from every token.  Row-for-row the same arithmetic as _block_fwd.
-        With xb / st (/ lo) -- the bf16 operand view, norm1 statistics (and low plane) the previous folded block left -- norm1 is folded into
-        the K|V GEMM like in every other block of the tower (no LayerNorm pass over the 403 456-row stream, the stream never returns to
-        fp32) and only the B CLS rows are rebuilt in fp32 for the query, the residual adds and the MLP."""
-        ops, cfg = self.ops, self.cfg
-        C, H, eps = cfg.width, cfg.heads, cfg.ln_eps
-        b = f"{self.prefix}blocks.{i}."
-        M = B * N
-        wqkv, bqkv = self._qkv_w(b)
-        kv = ops.empty((M, 2 * C), BF16)
-        q = ops.empty((B, C), BF16)
-        if xb is not None:
-            Wq, cq, dq = self.fold[i]["qkv"]
-            ops.gemm_nt_ln(xb, Wq[C:], kv, bias=dq[C:], ln_mean=st[0], ln_rstd=st[1], ln_colsum=cq[C:], epi=EPI_BF16)
-            xc = (self._join_planes(xb.view(B, N, C)[:, 0, :], lo.view(B, N, C)[:, 0, :]) if lo is not None
-                  else x.view(B, N, C)[:, 0, :].contiguous())
-            ln1c = ops.empty((B, C), BF16)
-            ops.layernorm_fwd(xc, self.p[b + "norm1.weight"], self.p[b + "norm1.bias"], ln1c, None, None, eps)
-            ops.gemm_nt(ln1c, wqkv[:C], q, bias=bqkv[:C], epi=EPI_BF16)
-        else:
-            ln1 = ops.empty((M, C), BF16)
-            ops.layernorm_fwd(x, self.p[b + "norm1.weight"], self.p[b + "norm1.bias"], ln1, None, None, eps)
-            ops.gemm_nt(ln1, wqkv[C:], kv, bias=bqkv[C:], epi=EPI_BF16)
-            ops.gemm_nt(ln1.view(B, N, C)[:, 0, :], wqkv[:C], q, bias=bqkv[:C], epi=EPI_BF16)
-            xc = x.view(B, N, C)[:, 0, :].contiguous()
-        att = ops.empty((B, C), BF16)
-        ops.attn_cls_fwd(q, kv, cos, sin, att, B, N, H, cfg.head_width ** -0.5)
-        return self._block_post(i, b, xc, att, B, lambda: (None, None), None, True)
-
     # ------------------------------------------------------------------------------------------ backward
     def _block_bwd(self, i, s, g, gb, B, N, cos, sin, ws, next_bias=None, gq=None):
         """g: fp32 [M,C] gradient w.r.t. the block output; updated in place to the gradient w.r.t. its input.  gb: its bf16 copy, already
@@ -496,31 +451,29 @@ class EvaEngine(TowerEngine):
         q8a = dict(q8=gq[0], q_scale=gq[1]) if gq is not None else {}
         ops, cfg = self.ops, self.cfg
         C, Hd, Hl, H = cfg.width, self.Hp, cfg.hidden, cfg.heads
-        padded = Hd != Hl
-        b = f"{self.prefix}blocks.{i}."
+        b = self._b(i)
         M = B * N
         G = self.g
         # ---- MLP: x2 = x1 + w3(ffn_ln(silu(x1')*x2')) ------------------------------------------
         self._wgrad(gb, s["fln"], self.storage_of(self.grad, b + "mlp.w3.weight"))
         d_fln = ops.empty((M, Hd), BF16)
         self._dgrad(i, "w3", gb, d_fln, q=gq)                                               # [M,C] . W3[C,Hd]
-        d_hid = (ops.zeros if padded else ops.empty)((M, Hd), BF16)
+        d_hid = (ops.zeros if Hd != Hl else ops.empty)((M, Hd), BF16)
         ops.layernorm_bwd(d_fln[:, :Hl], s["hid"][:, :Hl], self.p[b + "mlp.ffn_ln.weight"], *s["st4"], d_hid[:, :Hl], DX_BF16,
                           G[b + "mlp.ffn_ln.weight"], G[b + "mlp.ffn_ln.bias"], True, ws[0])
         d_x12 = ops.empty((M, 2 * Hd), BF16)
-        ob = self.offsets[b + "mlp.w1.bias"][0]
+        g12b = self._stacked(self.grad, "mlp.w1.bias", i)
         q12 = None
         if self.fp8_dgrad and Hd <= 4096:
             q12 = (ops.empty((M, _round_up(2 * Hd, 128)), torch.uint8), ops.empty((M,), F32))
             ops.swiglu_bwd(d_hid, s["x12"], d_x12, q8=q12[0], q_scale=q12[1])
-            ops.colsum_bf16(d_x12, self.grad[ob:ob + 2 * Hd], ws[1])
+            ops.colsum_bf16(d_x12, g12b, ws[1])
         elif self.fused_swiglu_colsum:
-            ops.swiglu_bwd_colsum(d_hid, s["x12"], d_x12, self.grad[ob:ob + 2 * Hd], ws[1])      # d x1|x2 and the w1 | w2 bias gradients in one pass
+            ops.swiglu_bwd_colsum(d_hid, s["x12"], d_x12, g12b, ws[1])      # d x1|x2 and the w1 | w2 bias gradients in one pass
         else:
             ops.swiglu_bwd(d_hid, s["x12"], d_x12)
-            ops.colsum_bf16(d_x12, self.grad[ob:ob + 2 * Hd], ws[1])
-        ow = self.offsets[b + "mlp.w1.weight"][0]
-        self._wgrad(d_x12, s["ln2"], self.grad[ow:ow + 2 * Hd * C].view(2 * Hd, C))
+            ops.colsum_bf16(d_x12, g12b, ws[1])
+        self._wgrad(d_x12, s["ln2"], self._stacked(self.grad, "mlp.w1.weight", i))
         d_ln2 = ops.empty((M, C), BF16)
         self._dgrad(i, "w12", d_x12, d_ln2, q=q12)                                          # [M,2Hd] . W12[2Hd,C]
         # norm2's backward adds into the stream gradient and hands back its bf16 copy + column sums (= the proj bias gradient)
@@ -533,17 +486,16 @@ class EvaEngine(TowerEngine):
         d_att = ops.empty((M, C), BF16)
         ops.layernorm_bwd(d_iln, s["att"], self.p[b + "attn.inner_attn_ln.weight"], *s["st2"], d_att, DX_BF16,
                           G[b + "attn.inner_attn_ln.weight"], G[b + "attn.inner_attn_ln.bias"], True, ws[0])
-        oq = self.offsets[b + "attn.q_proj.weight"][0]
         d_ln1 = ops.empty((M, C), BF16)
         if s["with_attn"]:
             d_qkv = ops.empty((M, 3 * C), BF16)
             ops.attn_bwd(s["qkv"], s["att"], d_att, s["lse"], cos, sin, d_qkv, ws[0], B, N, H, cfg.head_width ** -0.5)
             # one pass over d_q|d_k|d_v into the adjacent [q_bias; (k: no bias, eva_vit_model.py:178); v_bias] gradient slots; the middle slot
             # belongs to no parameter and goes back to zero (the flat gradient's norm must be the parameters' gradient norm)
-            obq = self.offsets[b + "attn.q_bias"][0]
-            ops.colsum_bf16(d_qkv, self.grad[obq:obq + 3 * C], ws[1])
-            self.grad[obq + C:obq + 2 * C].zero_()
-            self._wgrad(d_qkv, s["ln1"], self.grad[oq:oq + 3 * C * C].view(3 * C, C))
+            gqb = self._stacked(self.grad, "attn.q_bias", i)
+            ops.colsum_bf16(d_qkv, gqb, ws[1])
+            gqb[C:2 * C].zero_()
+            self._wgrad(d_qkv, s["ln1"], self._stacked(self.grad, "attn.q_proj.weight", i))
             self._dgrad(i, "qkv", d_qkv, d_ln1)
         else:
             ops.colsum_bf16(d_att, G[b + "attn.v_bias"], ws[1])

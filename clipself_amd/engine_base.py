@@ -35,15 +35,19 @@ def is_no_decay(name: str, ndim: int) -> bool:
 
 class TowerEngine:
     """A family supplies, besides its layout (`_layout`), stem (`_stem`, `_stem_bwd`), blocks (`_block_fwd`, `_teacher_block_folded`,
-    `_block_fwd_cls`, `_block_bwd`), `rope_tables`, `sync_transposed` and `_build_folds` -- each family writes the half of its block behind
-    the attention core once (engine.py: `_block_post`, engine_openai.py: `block_fwd_mlp`), and both `_teacher_block_folded` issue their
-    residual GEMMs through `_resid_gemm_folded` here:
-      names    BLOCK_TAG, FINAL_NORM, RESID_BIAS, _pos_table(views)
+    `_block_bwd`), `rope_tables`, `sync_transposed` and `_build_folds`, the hooks below.  What both families schedule alike is written once
+    here on those hooks: the CLS-only last block (`_block_fwd_cls`), the q|k|v GEMM and the residual GEMMs of `_teacher_block_folded`
+    (`_teacher_qkv`, `_resid_gemm_folded`), the head of the backward pass (`_bwd_workspaces`, `_final_norm_bwd`) and the W^T shadows of
+    the trainable blocks (`_block_wt_pairs`).
+      names    BLOCK_TAG, NORM1, FINAL_NORM, RESID_BIAS, _pos_table(views)
+      blocks   _qkv_operands (the stacked q|k|v matrix and bias), _block_tail (the block behind the attention core, for whichever rows
+               it is given), _block_linears (the four linears of a block: key, bf16 matrix)
       head     _head (forward), _head_dgrad, _head_wgrad (the train-all weight / bias gradients)
       teacher  _fold_pass (does this pass fold?), _cls_block_folds, _lo_plane (is the low plane of the split stream allocated?)
       student  _bwd_widths (LayerNorm / column-sum workspace widths), _bwd_gq
       shadows  HEAD_FWD_TRANSPOSED, _wants_folds (what sync_shadow rebuilds for a frozen tower)"""
     BLOCK_TAG = None                          # state-dict name of the block list below the tower prefix
+    NORM1 = None                              # ... of a block's first LayerNorm below the block's prefix
     FINAL_NORM = None                         # ... of the final LayerNorm
     RESID_BIAS = None                         # tail of a block's second residual bias: its gradient comes out of the LayerNorm backwards
     HEAD_FWD_TRANSPOSED = False               # does the forward head GEMM read a transposed shadow (then frozen towers need sync_transposed too)
@@ -52,6 +56,10 @@ class TowerEngine:
         """Index of the transformer block a state-dict name belongs to, None for stem / head tensors."""
         tag = self.prefix + self.BLOCK_TAG
         return int(name[len(tag):].split(".")[0]) if name.startswith(tag) else None
+
+    def _b(self, i: int) -> str:
+        """State-dict name prefix of block i."""
+        return f"{self.prefix}{self.BLOCK_TAG}{i}."
 
     def _never_reached(self, i: int, name: str) -> bool:
         """Tensors of block i the dense path never differentiates (none, unless a family says otherwise)."""
@@ -192,6 +200,12 @@ class TowerEngine:
             t = self.ops.zeros((cols, _round_up(rows, 64)), BF16)
             self.wt[key] = t
         return t
+
+    def _block_wt_pairs(self, blocks=None):
+        """(W, its W^T shadow) for every linear of the trainable blocks (or of `blocks`), in block order: the dgrad operands' part of the
+        list a family's sync_transposed hands to the one batched transpose."""
+        blocks = range(self.first_trainable, self.cfg.layers) if blocks is None else blocks
+        return [(W, self._wt_alloc((i, key), *W.shape)) for i in blocks for key, W in self._block_linears(i)]
 
     def set_trainable_blocks(self, unlocked_groups: int):
         """visual.lock(unlocked_groups) (eva_vit_model.py:500-516): only the last n blocks train
@@ -426,6 +440,57 @@ class TowerEngine:
             ops.gemm_nt_ln(A, W, x, bias=bias, extra=x, ln_mean=mean, ln_rstd=rstd, ln_colsum=colsum, stats_part=None if last else part,
                            xb_out=None if last else xb, epi=EPI_RESID_LN_F32 if ln is not None else EPI_RESID_F32)
 
+    def _row_stats(self, rows, keep):
+        """(mean, rstd) buffers fp32 [rows] for a LayerNorm whose backward will run, else (None, None)."""
+        return (self.ops.empty((rows,), F32), self.ops.empty((rows,), F32)) if keep else (None, None)
+
+    def _teacher_qkv(self, i, x, xb, st, M):
+        """q|k|v bf16 [M, 3C] of a _teacher_block_folded: the first block of the tower (xb None) runs the plain LayerNorm and GEMM on fp32 x,
+        every later one the GEMM with the LayerNorm folded, on the bf16 copy xb and the statistics st the previous block left."""
+        ops, C, n1 = self.ops, self.cfg.width, self._b(i) + self.NORM1
+        qkv = ops.empty((M, 3 * C), BF16)
+        if xb is None:
+            ln1 = ops.empty((M, C), BF16)
+            ops.layernorm_fwd(x, self.p[n1 + ".weight"], self.p[n1 + ".bias"], ln1, None, None, self.cfg.ln_eps)
+            wqkv, bqkv = self._qkv_operands(i)
+            ops.gemm_nt(ln1, wqkv, qkv, bias=bqkv, epi=EPI_BF16)
+        else:
+            Wq, cq, dq = self.fold[i]["qkv"]
+            ops.gemm_nt_ln(xb, Wq, qkv, bias=dq, ln_mean=st[0], ln_rstd=st[1], ln_colsum=cq, epi=EPI_BF16)
+        return qkv
+
+    def _block_fwd_cls(self, i, x, B, N, cos, sin, xb=None, st=None, lo=None):
+        """Last teacher block restricted to what encode_image() consumes: the CLS row.  x fp32 [B*N, C] -> fp32 [B, C].  The tower returns
+        x[:, 0] after the final norm (eva_vit_model.py:505-519, transformer.py:486-494), so only the CLS *query* of the last block is live;
+        keys and values still come from every token.  Row-for-row the same arithmetic as _block_fwd.
+        With xb / st (/ lo) -- the bf16 operand view, first-LayerNorm statistics (and low plane) the previous folded block left -- that
+        LayerNorm is folded into the K|V GEMM like in every other block of the tower (no LayerNorm pass over the 403 456-row stream, the
+        stream never returns to fp32) and only the B CLS rows are rebuilt in fp32 for the query, the residual adds and the MLP."""
+        ops, cfg = self.ops, self.cfg
+        C, H, eps = cfg.width, cfg.heads, cfg.ln_eps
+        n1 = self._b(i) + self.NORM1
+        M = B * N
+        wqkv, bqkv = self._qkv_operands(i)
+        kv = ops.empty((M, 2 * C), BF16)
+        q = ops.empty((B, C), BF16)
+        if xb is not None:
+            Wq, cq, dq = self.fold[i]["qkv"]
+            ops.gemm_nt_ln(xb, Wq[C:], kv, bias=dq[C:], ln_mean=st[0], ln_rstd=st[1], ln_colsum=cq[C:], epi=EPI_BF16)
+            xc = (self._join_planes(xb.view(B, N, C)[:, 0, :], lo.view(B, N, C)[:, 0, :]) if lo is not None
+                  else x.view(B, N, C)[:, 0, :].contiguous())
+            ln1c = ops.empty((B, C), BF16)
+            ops.layernorm_fwd(xc, self.p[n1 + ".weight"], self.p[n1 + ".bias"], ln1c, None, None, eps)
+            ops.gemm_nt(ln1c, wqkv[:C], q, bias=bqkv[:C], epi=EPI_BF16)
+        else:
+            ln1 = ops.empty((M, C), BF16)
+            ops.layernorm_fwd(x, self.p[n1 + ".weight"], self.p[n1 + ".bias"], ln1, None, None, eps)
+            ops.gemm_nt(ln1, wqkv[C:], kv, bias=bqkv[C:], epi=EPI_BF16)
+            ops.gemm_nt(ln1.view(B, N, C)[:, 0, :], wqkv[:C], q, bias=bqkv[:C], epi=EPI_BF16)
+            xc = x.view(B, N, C)[:, 0, :].contiguous()
+        att = ops.empty((B, C), BF16)
+        ops.attn_cls_fwd(q, kv, cos, sin, att, B, N, H, cfg.head_width ** -0.5)
+        return self._block_tail(i, xc, att)
+
     def encode_image(self, images, chunk: int = 256):
         """Frozen-teacher path: full ViT, final LN on the CLS row, head.  [K,3,S,S] -> fp32 [K,E].
         Activation-free: crops are streamed in chunks, blocks update the residual stream in place."""
@@ -579,10 +644,38 @@ class TowerEngine:
         """(e4m3 codes, row scales) buffers for the bf16 copy of the stream gradient, or None (no fp8 dgrad)."""
         return None
 
+    def _bwd_workspaces(self, M, B, N, Q=0):
+        """ws of a backward pass over M rows: (LayerNorm-backward / attention-backward scratch, column-sum scratch), uint8.  Q: extra query
+        rows per image in the attention backward (mask-attention pooling)."""
+        ops = self.ops
+        ln_width, colsum_width = self._bwd_widths()
+        extra = (Q,) if Q else ()                     # (a backend without extra query rows takes no Q)
+        ws_bytes = max(ops.layernorm_bwd_workspace(M, ln_width), ops.attn_bwd_workspace(B, N, self.cfg.heads, *extra))
+        return ops.empty((ws_bytes,), torch.uint8), ops.empty((max(ops.colsum_workspace(M, colsum_width), 4),), torch.uint8)
+
+    def _resid_bias(self, i):
+        """Gradient slot of block i's second residual bias, None for a frozen block."""
+        return self.g[self._b(i) + self.RESID_BIAS] if i >= self.first_trainable else None
+
+    def _final_norm_bwd(self, c, d_feats, d_lnf, g, gb, ws, gq=None):
+        """Head of a backward pass, from the context c of its forward: with train_all the head's weight gradient and the final norm's gamma /
+        beta gradients (then the "head" bucket is complete); in either case g = the gradient w.r.t. the last block's output, assigned.  Its
+        bf16 copy gb (and e4m3 copy gq), whose column sums are the last block's second residual bias gradient, is wanted when a block trains."""
+        L, fn = self.cfg.layers, self.prefix + self.FINAL_NORM
+        if self.train_all:
+            self._head_wgrad(d_feats, c["lnf"], ws)
+        dgamma, dbeta = (self.g[fn + ".weight"], self.g[fn + ".bias"]) if self.train_all else (None, None)
+        copy = self.first_trainable < L
+        q8a = dict(q8=gq[0], q_scale=gq[1]) if gq is not None and copy else {}
+        self.ops.layernorm_bwd(d_lnf, c["xL"], self.p[fn + ".weight"], *c["stf"], g, DX_F32_ASSIGN, dgamma, dbeta, True, ws[0],
+                               dx_copy=gb if copy else None, copy_colsum=self._resid_bias(L - 1), **q8a)
+        if self.train_all and self.grad_ready_hook is not None:
+            self.grad_ready_hook("head")
+
     def backward_dense(self, d_dense):
         """d_dense: fp32 [B, N, E] gradient w.r.t. the normalised token map (CLS rows zero).  Accumulates every trainable gradient into the
         flat grad buffer; fires grad_ready_hook("head" / block index / "stem") as buckets complete."""
-        ops, cfg, P = self.ops, self.cfg, self.prefix
+        ops, cfg = self.ops, self.cfg
         c = self._ctx
         if c is None:
             raise RuntimeError("backward_dense() without a preceding encode_dense(need_grad=True)")
@@ -596,24 +689,11 @@ class TowerEngine:
         g = ops.empty((M, C), F32)
         gb = ops.empty((M, C), BF16)                  # bf16 copy of g, written by the LayerNorm backwards that update g
         gq = self._bwd_gq(M)
-        q8a = dict(q8=gq[0], q_scale=gq[1]) if gq is not None else {}
-        ln_width, colsum_width = self._bwd_widths()
-        ws_bytes = max(ops.layernorm_bwd_workspace(M, ln_width), ops.attn_bwd_workspace(B, N, cfg.heads))
-        ws = (ops.empty((ws_bytes,), torch.uint8), ops.empty((max(ops.colsum_workspace(M, colsum_width), 4),), torch.uint8))
-        L, first, fn = cfg.layers, self.first_trainable, P + self.FINAL_NORM
-        resid_bias = lambda i: self.g[f"{P}{self.BLOCK_TAG}{i}.{self.RESID_BIAS}"] if i >= first else None
-        if self.train_all:
-            # head and final norm train.  The CLS rows of d_feats are exact zeros (the dense map drops them), so they add nothing to any sum.
-            self._head_wgrad(d_feats, c["lnf"], ws)
-            ops.layernorm_bwd(d_lnf, c["xL"], self.p[fn + ".weight"], *c["stf"], g, DX_F32_ASSIGN,
-                              self.g[fn + ".weight"], self.g[fn + ".bias"], True, ws[0], dx_copy=gb, copy_colsum=resid_bias(L - 1), **q8a)
-            if self.grad_ready_hook is not None:
-                self.grad_ready_hook("head")
-        else:                                                                                   # head and final norm frozen
-            ops.layernorm_bwd(d_lnf, c["xL"], self.p[fn + ".weight"], *c["stf"], g, DX_F32_ASSIGN, None, None, True, ws[0],
-                              dx_copy=gb if first < L else None, copy_colsum=resid_bias(L - 1), **(q8a if first < L else {}))
-        for i in range(L - 1, first - 1, -1):
-            self._block_bwd(i, c["saves"].pop(i), g, gb, B, N, c["cos"], c["sin"], ws, next_bias=resid_bias(i - 1) if i > 0 else None, gq=gq)
+        ws = self._bwd_workspaces(M, B, N)
+        # (the CLS rows of d_feats are exact zeros -- the dense map drops them --, so they add nothing to any sum of the head's gradients)
+        self._final_norm_bwd(c, d_feats, d_lnf, g, gb, ws, gq)
+        for i in range(cfg.layers - 1, self.first_trainable - 1, -1):
+            self._block_bwd(i, c["saves"].pop(i), g, gb, B, N, c["cos"], c["sin"], ws, next_bias=self._resid_bias(i - 1) if i > 0 else None, gq=gq)
             if self.grad_ready_hook is not None:
                 self.grad_ready_hook(i)
         if c["stem"] is not None:

@@ -14,12 +14,14 @@ does each stage (paths under /root/reference/src/open_clip/):
   lock            transformer.py:391-422     groups = [stem, positional_embedding, blocks..., last block]; the last n train
                                              (n > L: positional_embedding, then conv1 / class_embedding / ln_pre: _stem_bwd)
 
-The frozen teacher runs TowerEngine.encode_image like the EVA02 one: CLS-query-only last block, ln_1 / ln_2 folded into the in_proj / c_fc
-GEMMs with the residual GEMMs emitting the bf16 copy and the row statistics of the stream (`_teacher_block_folded`).
+The frozen teacher runs TowerEngine.encode_image like the EVA02 one: CLS-query-only last block (TowerEngine._block_fwd_cls), ln_1 / ln_2
+folded into the in_proj / c_fc GEMMs with the residual GEMMs emitting the bf16 copy and the row statistics of the stream
+(`_teacher_block_folded`).  The head of the backward pass (workspaces, ln_post, proj) is TowerEngine's too, for backward_dense and
+backward_mask_attn alike.
 
 The block's forward behind the attention core -- out_proj (+x), ln_2, c_fc + activation, c_proj (+x1) -- is written once, in block_fwd_mlp
-below (the twin of _block_bwd_mlp): every row set of this engine runs it (image tokens, the CLS rows, mask-attention passengers) and so
-does the text tower (engine_text.py).
+below (the twin of _block_bwd_mlp): every row set of this engine runs it through `_block_tail` (image tokens, the CLS rows, mask-attention
+passengers) and so does the text tower (engine_text.py).
 
 Differences to the EVA02 schedule: no RoPE (the attention kernels run without tables: rope_tables), no sub-LayerNorms, `proj` is a bias-free
 [C,E] matrix kept transposed for the forward GEMM, and the last dense block owns no never-reached *tensor* (q/k are rows of the one
@@ -44,7 +46,7 @@ def clip_vit_layout(cfg: TowerCfg, prefix: str = "visual."):
     groups = [[t(prefix + "class_embedding", (C,))], [t(prefix + "positional_embedding", (cfg.tokens, C))],
               [t(prefix + "conv1.weight", (C, 3, p, p), (C, Kp))], [t(prefix + "ln_pre.weight", (C,))], [t(prefix + "ln_pre.bias", (C,))]]
     for i in range(cfg.layers):
-        b = f"{prefix}transformer.resblocks.{i}."
+        b = f"{prefix}{ClipVitEngine.BLOCK_TAG}{i}."
         groups += [[t(b + "ln_1.weight", (C,))], [t(b + "ln_1.bias", (C,))],
                    [t(b + "attn.in_proj_weight", (3 * C, C))], [t(b + "attn.in_proj_bias", (3 * C,))],
                    [t(b + "attn.out_proj.weight", (C, C))], [t(b + "attn.out_proj.bias", (C,))],
@@ -88,7 +90,7 @@ def block_fwd_mlp(ops, p, w, b, eps, quick_gelu, x, att, save=None, inplace=True
 
 
 class ClipVitEngine(TowerEngine):
-    BLOCK_TAG, FINAL_NORM, RESID_BIAS = "transformer.resblocks.", "ln_post", "mlp.c_proj.bias"
+    BLOCK_TAG, NORM1, FINAL_NORM, RESID_BIAS = "transformer.resblocks.", "ln_1", "ln_post", "mlp.c_proj.bias"
     HEAD_FWD_TRANSPOSED = True                                  # proj^T serves the forward head GEMM of frozen towers too
 
     def __init__(self, cfg: TowerCfg, ops, trainable: bool = False, prefix: str = "visual."):
@@ -132,23 +134,26 @@ class ClipVitEngine(TowerEngine):
     # ------------------------------------------------------------------------------------------ parameters
     def sync_transposed(self, blocks=None):
         """proj^T [E,C] for the forward head GEMM (every tower), and W^T shadows of the trainable blocks for the dgrad GEMMs."""
-        cfg, C, Hd = self.cfg, self.cfg.width, self.cfg.hidden
-        pairs = [(self.w[self.prefix + "proj"], self._wt_alloc("head_fwd", C, cfg.embed_dim))]
+        pairs = [(self.w[self.prefix + "proj"], self._wt_alloc("head_fwd", self.cfg.width, self.cfg.embed_dim))]
         if self.trainable:
-            for i in (range(self.first_trainable, cfg.layers) if blocks is None else blocks):
-                b = f"{self.prefix}{self.BLOCK_TAG}{i}."
-                pairs.append((self.w[b + "attn.in_proj_weight"], self._wt_alloc((i, "qkv"), 3 * C, C)))
-                pairs.append((self.w[b + "attn.out_proj.weight"], self._wt_alloc((i, "proj"), C, C)))
-                pairs.append((self.w[b + "mlp.c_fc.weight"], self._wt_alloc((i, "fc"), Hd, C)))
-                pairs.append((self.w[b + "mlp.c_proj.weight"], self._wt_alloc((i, "cproj"), C, Hd)))
+            pairs += self._block_wt_pairs(blocks)
         self.ops.transpose_bf16_batched(pairs)
+
+    def _block_linears(self, i):
+        b = self._b(i)
+        return (("qkv", self.w[b + "attn.in_proj_weight"]), ("proj", self.w[b + "attn.out_proj.weight"]),
+                ("fc", self.w[b + "mlp.c_fc.weight"]), ("cproj", self.w[b + "mlp.c_proj.weight"]))
+
+    def _qkv_operands(self, i):
+        b = self._b(i)
+        return self.w[b + "attn.in_proj_weight"], self.p[b + "attn.in_proj_bias"]
 
     def _build_folds(self):
         """gamma (.) W in bf16, its row sums and W.beta + b for ln_1 -> in_proj and ln_2 -> c_fc of every block (one-time, after a load)."""
         self.fold = {}
         with torch.no_grad():
             for i in range(self.cfg.layers):
-                b = f"{self.prefix}{self.BLOCK_TAG}{i}."
+                b = self._b(i)
                 out = {}
                 for key, wname, bname, ln in (("qkv", "attn.in_proj_weight", "attn.in_proj_bias", "ln_1"), ("fc", "mlp.c_fc.weight", "mlp.c_fc.bias", "ln_2")):
                     W, bias = self.p[b + wname], self.p[b + bname]
@@ -220,21 +225,21 @@ class ClipVitEngine(TowerEngine):
         ops.layernorm_fwd_f32(x.view(B * N, C), self.p[P + "ln_pre.weight"], self.p[P + "ln_pre.bias"], y.view(B * N, C), mean, rstd, cfg.ln_eps)
         return y, g
 
-    def _block_fwd_mlp(self, b, x, att, save=None, inplace=True):
+    def _block_tail(self, i, x, att, save=None, inplace=True):
         """block_fwd_mlp on this tower's parameters: the forward twin of _block_bwd_mlp, for whichever rows x holds."""
-        return block_fwd_mlp(self.ops, self.p, self.w, b, self.cfg.ln_eps, self.cfg.quick_gelu, x, att, save, inplace)
+        return block_fwd_mlp(self.ops, self.p, self.w, self._b(i), self.cfg.ln_eps, self.cfg.quick_gelu, x, att, save, inplace)
 
     def _block_fwd(self, i, x, B, N, cos, sin, with_attn=True, save=None, inplace=True):
         ops, cfg = self.ops, self.cfg
         C, H, eps = cfg.width, cfg.heads, cfg.ln_eps
-        b = f"{self.prefix}{self.BLOCK_TAG}{i}."
+        b = self._b(i)
         M = B * N
         keep = save is not None
 
         ln1 = ops.empty((M, C), BF16)
-        m1, r1 = (ops.empty((M,), F32), ops.empty((M,), F32)) if keep else (None, None)
+        m1, r1 = self._row_stats(M, keep)
         ops.layernorm_fwd(x, self.p[b + "ln_1.weight"], self.p[b + "ln_1.bias"], ln1, m1, r1, eps)
-        wqkv, bqkv = self.w[b + "attn.in_proj_weight"], self.p[b + "attn.in_proj_bias"]
+        wqkv, bqkv = self._qkv_operands(i)
         qkv = lse = None
         att = ops.empty((M, C), BF16)
         if with_attn:
@@ -246,7 +251,7 @@ class ClipVitEngine(TowerEngine):
             ops.gemm_nt(ln1, wqkv[2 * C:], att, bias=bqkv[2 * C:], epi=EPI_BF16)        # proj_without_attn: the value rows only
         if keep:
             save.update(x0=x, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, att=att, with_attn=with_attn)
-        return self._block_fwd_mlp(b, x, att, save, inplace)
+        return self._block_tail(i, x, att, save, inplace)
 
     def _teacher_block_folded(self, i, x, xb, st, B, N, cos, sin, emit_next, lo=None):
         """One frozen-tower block with both LayerNorms folded into the GEMMs (in place on x).  xb / st = bf16 copy and (mean, rstd) of x as
@@ -257,18 +262,10 @@ class ClipVitEngine(TowerEngine):
         out_proj / c_proj (ln=None of _resid_gemm_folded), so the split kernel gets the identity statistics (mean 0, rstd 1, column sums 0: x + 1 * (acc - 0 * 0) + b)."""
         ops, cfg = self.ops, self.cfg
         C, Hd, H, eps = cfg.width, cfg.hidden, cfg.heads, cfg.ln_eps
-        b = f"{self.prefix}{self.BLOCK_TAG}{i}."
+        b = self._b(i)
         M = B * N
-        f = self.fold[i]
-        qkv = ops.empty((M, 3 * C), BF16)
         first = xb is None
-        if first:
-            ln1 = ops.empty((M, C), BF16)
-            ops.layernorm_fwd(x, self.p[b + "ln_1.weight"], self.p[b + "ln_1.bias"], ln1, None, None, eps)
-            ops.gemm_nt(ln1, self.w[b + "attn.in_proj_weight"], qkv, bias=self.p[b + "attn.in_proj_bias"], epi=EPI_BF16)
-        else:
-            Wq, cq, dq = f["qkv"]
-            ops.gemm_nt_ln(xb, Wq, qkv, bias=dq, ln_mean=st[0], ln_rstd=st[1], ln_colsum=cq, epi=EPI_BF16)
+        qkv = self._teacher_qkv(i, x, xb, st, M)
         att = ops.empty((M, C), BF16)
         ops.attn_fwd(qkv, cos, sin, att, None, B, N, H, cfg.head_width ** -0.5)
         part = ops.empty(((C + 63) // 64, M, 2), F32)
@@ -276,7 +273,7 @@ class ClipVitEngine(TowerEngine):
         self._resid_gemm_folded(att, self.w[b + "attn.out_proj.weight"], self.p[b + "attn.out_proj.bias"], None, x, xb2, lo, part, first=first)
         mean, rstd = ops.empty((M,), F32), ops.empty((M,), F32)
         ops.ln_stats_finalize(part, 64, C, mean, rstd, eps)
-        Wf, cf, df = f["fc"]
+        Wf, cf, df = self.fold[i]["fc"]
         hid = ops.empty((M, Hd), BF16)
         ops.gemm_nt_ln(xb2, Wf, hid, bias=df, ln_mean=mean, ln_rstd=rstd, ln_colsum=cf, epi=act_epilogue(cfg.quick_gelu))
         self._resid_gemm_folded(hid, self.w[b + "mlp.c_proj.weight"], self.p[b + "mlp.c_proj.bias"], None, x, xb2, lo, part, last=not emit_next)
@@ -284,36 +281,6 @@ class ClipVitEngine(TowerEngine):
             return None, None
         ops.ln_stats_finalize(part, 64, C, mean, rstd, eps)
         return xb2, (mean, rstd)
-
-    def _block_fwd_cls(self, i, x, B, N, cos, sin, xb=None, st=None, lo=None):
-        """Last teacher block restricted to what forward() consumes: the CLS row.  x fp32 [B*N, C] -> fp32 [B, C]; keys and values still
-        come from every token.  Row-for-row the same arithmetic as _block_fwd.  With xb / st (/ lo) -- the bf16 operand view, ln_1 statistics
-        (and low plane) the previous folded block left -- ln_1 is folded into the K|V GEMM like in every other block (no LayerNorm pass over
-        the whole stream, which never returns to fp32) and only the B CLS rows are rebuilt in fp32."""
-        ops, cfg = self.ops, self.cfg
-        C, H, eps = cfg.width, cfg.heads, cfg.ln_eps
-        b = f"{self.prefix}{self.BLOCK_TAG}{i}."
-        M = B * N
-        wqkv, bqkv = self.w[b + "attn.in_proj_weight"], self.p[b + "attn.in_proj_bias"]
-        kv = ops.empty((M, 2 * C), BF16)
-        q = ops.empty((B, C), BF16)
-        if xb is not None:
-            Wq, cq, dq = self.fold[i]["qkv"]
-            ops.gemm_nt_ln(xb, Wq[C:], kv, bias=dq[C:], ln_mean=st[0], ln_rstd=st[1], ln_colsum=cq[C:], epi=EPI_BF16)
-            xc = (self._join_planes(xb.view(B, N, C)[:, 0, :], lo.view(B, N, C)[:, 0, :]) if lo is not None
-                  else x.view(B, N, C)[:, 0, :].contiguous())
-            ln1c = ops.empty((B, C), BF16)
-            ops.layernorm_fwd(xc, self.p[b + "ln_1.weight"], self.p[b + "ln_1.bias"], ln1c, None, None, eps)
-            ops.gemm_nt(ln1c, wqkv[:C], q, bias=bqkv[:C], epi=EPI_BF16)
-        else:
-            ln1 = ops.empty((M, C), BF16)
-            ops.layernorm_fwd(x, self.p[b + "ln_1.weight"], self.p[b + "ln_1.bias"], ln1, None, None, eps)
-            ops.gemm_nt(ln1, wqkv[C:], kv, bias=bqkv[C:], epi=EPI_BF16)
-            ops.gemm_nt(ln1.view(B, N, C)[:, 0, :], wqkv[:C], q, bias=bqkv[:C], epi=EPI_BF16)
-            xc = x.view(B, N, C)[:, 0, :].contiguous()
-        att = ops.empty((B, C), BF16)
-        ops.attn_cls_fwd(q, kv, cos, sin, att, B, N, H, cfg.head_width ** -0.5)
-        return self._block_fwd_mlp(b, xc, att)
 
     # ------------------------------------------------------------------------------------------ mask-attention pooling (inference)
     def _allow_table(self, masks, B, Q, N, g):
@@ -354,8 +321,8 @@ class ClipVitEngine(TowerEngine):
             xm = x[:, :1, :].expand(B, Q, C).reshape(B * Q, C).contiguous()          # fp32 passenger stream
             MQ = B * Q
             for i in range(cfg.layers):
-                b_ = f"{P}{self.BLOCK_TAG}{i}."
-                wqkv, bqkv = self.w[b_ + "attn.in_proj_weight"], self.p[b_ + "attn.in_proj_bias"]
+                b_ = self._b(i)
+                wqkv, bqkv = self._qkv_operands(i)
                 ln1 = ops.empty((B * N, C), BF16)
                 ops.layernorm_fwd(xf, self.p[b_ + "ln_1.weight"], self.p[b_ + "ln_1.bias"], ln1, None, None, eps)
                 qkv = ops.empty((B * N, 3 * C), BF16)
@@ -366,11 +333,11 @@ class ClipVitEngine(TowerEngine):
                 ops.gemm_nt(lnm, wqkv[:C], qm, bias=bqkv[:C], epi=EPI_BF16)
                 attm = ops.empty((MQ, C), BF16)
                 ops.attn_query_fwd(qm, qkv[:, C:], allow, attm, B, Q, N, H, cfg.head_width ** -0.5)
-                self._block_fwd_mlp(b_, xm, attm)
+                self._block_tail(i, xm, attm)
                 if i + 1 < cfg.layers:                      # the image tokens move on (they never see the passengers); not needed after the last block
                     att = ops.empty((B * N, C), BF16)
                     ops.attn_fwd(qkv, cos, sin, att, None, B, N, H, cfg.head_width ** -0.5)
-                    self._block_fwd_mlp(b_, xf, att)
+                    self._block_tail(i, xf, att)
             lnp = ops.empty((MQ, C), BF16)
             ops.layernorm_fwd(xm, self.p[P + "ln_post.weight"], self.p[P + "ln_post.bias"], lnp, None, None, eps)
             pooled = ops.empty((MQ, E), F32)
@@ -408,16 +375,17 @@ class ClipVitEngine(TowerEngine):
         xs[BN:] = x[:, :1, :].expand(B, Q, C).reshape(MQ, C)
         saves = {}
         for i in range(cfg.layers):
-            b_ = f"{P}{self.BLOCK_TAG}{i}."
+            b_ = self._b(i)
             last = i == cfg.layers - 1
             keep = i >= self.first_trainable
             R0 = BN if last else 0                                  # first row that continues past the attention
             R = M - R0
             ln1 = ops.empty((M, C), BF16)
-            m1, r1 = (ops.empty((M,), F32), ops.empty((M,), F32)) if keep else (None, None)
+            m1, r1 = self._row_stats(M, keep)
             ops.layernorm_fwd(xs, self.p[b_ + "ln_1.weight"], self.p[b_ + "ln_1.bias"], ln1, m1, r1, eps)
             qkv = ops.empty((M, 3 * C), BF16)
-            ops.gemm_nt(ln1, self.w[b_ + "attn.in_proj_weight"], qkv, bias=self.p[b_ + "attn.in_proj_bias"], epi=EPI_BF16)
+            wqkv, bqkv = self._qkv_operands(i)
+            ops.gemm_nt(ln1, wqkv, qkv, bias=bqkv, epi=EPI_BF16)
             att = ops.empty((R, C), BF16)
             lse = None
             if not last:
@@ -427,7 +395,7 @@ class ClipVitEngine(TowerEngine):
             ops.attn_query_fwd(qkv[BN:, :C], qkv[:BN, C:], allow, att[BN - R0:], B, Q, N, H, scale, **(dict(lse=lse_m) if keep else {}))
             if keep:
                 saves[i] = dict(x0=xs, ln1=ln1, st1=(m1, r1), qkv=qkv, lse=lse, lse_m=lse_m, att=att, with_attn=True, R0=R0)
-            xs = self._block_fwd_mlp(b_, xs[R0:], att, saves.get(i), inplace=not keep)
+            xs = self._block_tail(i, xs[R0:], att, saves.get(i), inplace=not keep)
         xm = xs                                                      # [B*Q, C]: what the last block left
         lnp = ops.empty((MQ, C), BF16)
         mean, rstd = ops.empty((MQ,), F32), ops.empty((MQ,), F32)
@@ -445,7 +413,7 @@ class ClipVitEngine(TowerEngine):
         row sets and cs_attn_bwd with the passengers as its `extra` rows (the last block: passengers only, no image rows), then the
         passengers' gradient at the input of block 0 joins their image's CLS row -- they started as copies of it -- ahead of the stem.
         Padding passengers carry a zero upstream gradient and contribute exact zeros.  Hooks fire in backward_dense's order."""
-        ops, cfg, P = self.ops, self.cfg, self.prefix
+        ops, cfg = self.ops, self.cfg
         c = self._ctx_mask
         if c is None:
             raise RuntimeError("backward_mask_attn() without a preceding mask_attn_pool(need_grad=True)")
@@ -463,22 +431,9 @@ class ClipVitEngine(TowerEngine):
         self._head_dgrad(d_feats, d_lnf)
         g = ops.zeros((M, C), F32)                    # image rows: nobody consumes the last block's image tokens
         gb = ops.zeros((M, C), BF16)
-        ln_width, colsum_width = self._bwd_widths()
-        ws_bytes = max(ops.layernorm_bwd_workspace(M, ln_width), ops.attn_bwd_workspace(B, N, H, Q))
-        ws = (ops.empty((ws_bytes,), torch.uint8), ops.empty((max(ops.colsum_workspace(M, colsum_width), 4),), torch.uint8))
-        L, first, fn = cfg.layers, self.first_trainable, P + self.FINAL_NORM
-        resid_bias = lambda i: self.g[f"{P}{self.BLOCK_TAG}{i}.{self.RESID_BIAS}"] if i >= first else None
-        gm, gbm = g[BN:], gb[BN:]
-        if self.train_all:
-            self._head_wgrad(d_feats, c["lnf"], ws)
-            ops.layernorm_bwd(d_lnf, c["xL"], self.p[fn + ".weight"], *c["stf"], gm, DX_F32_ASSIGN,
-                              self.g[fn + ".weight"], self.g[fn + ".bias"], True, ws[0], dx_copy=gbm, copy_colsum=resid_bias(L - 1))
-            if self.grad_ready_hook is not None:
-                self.grad_ready_hook("head")
-        else:
-            ops.layernorm_bwd(d_lnf, c["xL"], self.p[fn + ".weight"], *c["stf"], gm, DX_F32_ASSIGN, None, None, True, ws[0],
-                              dx_copy=gbm if first < L else None, copy_colsum=resid_bias(L - 1))
-        for i in range(L - 1, first - 1, -1):
+        ws = self._bwd_workspaces(M, B, N, Q)
+        self._final_norm_bwd(c, d_feats, d_lnf, g[BN:], gb[BN:], ws)                # the head saw the passenger rows alone
+        for i in range(cfg.layers - 1, self.first_trainable - 1, -1):
             s = c["saves"].pop(i)
             R0 = s["R0"]
             d_att = self._block_bwd_mlp(i, s, g[R0:], gb[R0:], ws)
@@ -491,7 +446,7 @@ class ClipVitEngine(TowerEngine):
                              extra=extra)
             else:
                 ops.attn_bwd(qkv[:BN], None, None, None, c["cos"], c["sin"], d_qkv[:BN], ws[0], B, N, H, cfg.head_width ** -0.5, extra=extra)
-            self._block_bwd_ln1(i, s, d_qkv, 0, g, gb, ws, next_bias=resid_bias(i - 1) if i > 0 else None)
+            self._block_bwd_ln1(i, s, d_qkv, 0, g, gb, ws, next_bias=self._resid_bias(i - 1) if i > 0 else None)
             if self.grad_ready_hook is not None:
                 self.grad_ready_hook(i)
         if c["stem"] is not None:
@@ -521,7 +476,7 @@ class ClipVitEngine(TowerEngine):
         bf16 copy, whose column sums go to out_proj's bias) and out_proj.  -> d_att, bf16 [rows, C]."""
         ops, cfg = self.ops, self.cfg
         C, Hd = cfg.width, cfg.hidden
-        b = f"{self.prefix}{self.BLOCK_TAG}{i}."
+        b = self._b(i)
         M = g.shape[0]
         G = self.g
         # ---- MLP: x2 = x1 + c_proj(act(c_fc(ln_2 x1))) --------------------------------------------
@@ -548,7 +503,7 @@ class ClipVitEngine(TowerEngine):
         _block_bwd)."""
         ops, cfg = self.ops, self.cfg
         C = cfg.width
-        b = f"{self.prefix}{self.BLOCK_TAG}{i}."
+        b = self._b(i)
         G = self.g
         d_ln1 = ops.empty((d.shape[0], C), BF16)
         ops.colsum_bf16(d, G[b + "attn.in_proj_bias"][col0:], ws[1])                         # q, k and v all carry a bias here
