@@ -79,6 +79,14 @@ SIGNATURES = {
 }
 
 
+# include/clipself_det.h: detector post-processing.  Not an engine op, so not part of SIGNATURES (which mirrors clipself_hip.h one to one)
+DET_SIGNATURES = {
+    "csd_nms_workspace": (_sz, [_i, _i, _i, _i]),
+    "csd_nms": (_i, [_vp, _l, _vp, _l, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csd_delta2bbox": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _f, _vp, _vp, _vp, _l, _vp]),
+}
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -108,9 +116,10 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
-            fn.restype, fn.argtypes = res, args
+        for table in (SIGNATURES, DET_SIGNATURES):
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
+                fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib
 
@@ -143,6 +152,7 @@ class HipOps:
     ATTN_NO_ROPE = True                 # attn_fwd / attn_fwd_stats / attn_cls_fwd / attn_bwd(cos=None, sin=None): no rotary embedding, any Ntok > 1
     TOKEN_TAPS = True                   # tokens_to_nchw: the residual stream after a block as a [B, C, h, w] map (encode_dense(taps=), the detector backbone)
     DECONV_ROWS = True                  # rows_to_nchw / nchw_to_rows: 2x2 transposed convolutions as GEMMs on token rows (neck.Deconv2x2)
+    DET_POST = True                     # nms / delta2bbox: box decoding, class-aware NMS and the per-image cut on the device (det_post)
     BOX_SCORES = True                   # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -717,6 +727,68 @@ class HipOps:
                                           _p(class_embed), C, float(vlm_temp), _p(det_logits), det_logits.stride(0) if det_logits is not None else 0,
                                           _p(expo) if det_logits is not None else None, _p(scores), scores.stride(0), self._stream()),
                  "cs_roialign_fwd")
+
+    # -- detector post-processing (include/clipself_det.h) ------------------------------------------
+    def nms_workspace(self, B, Kmax, C_or_G, max_num) -> int:
+        return int(self.lib.csd_nms_workspace(int(B), int(Kmax), int(C_or_G), int(max_num)))
+
+    def nms(self, boxes, scores, starts, Kmax, score_thr, iou_thr, max_num, group=None, G=0, out=None, workspace=None):
+        """Score threshold, per-list greedy NMS and the per-image cut (csd_nms): boxes [K, 4], scores [K, C] (foreground columns), starts
+        [B + 1] int32 on the device, group [K] int32 with G groups for the RPN form (C == 1).  -> (dets [B, max_num, 5], labels, inds
+        [B, max_num] int32, counts [B] int32): fixed shapes, nothing is read back.  The workspace is cached per shape (pass workspace= to
+        own it): after the first call of a shape the call allocates only its outputs (pass out= to own those too) and never
+        synchronises, which is what stream capture needs (the tests do not capture); calls that share a shape must share a stream."""
+        self._chk(boxes, scores, starts, group, workspace)
+        f32, i32 = torch.float32, torch.int32
+        K, C = scores.shape
+        B = starts.numel() - 1
+        assert boxes.dtype == f32 and boxes.dim() == 2 and boxes.shape == (K, 4) and (K == 0 or boxes.stride(1) == 1)
+        assert scores.dtype == f32 and (K == 0 or scores.stride(1) == 1)
+        assert starts.dtype == i32 and starts.is_contiguous() and B >= 1
+        assert group is None or (group.dtype == i32 and group.is_contiguous() and group.numel() == K)
+        ldb = boxes.stride(0) if K > 1 else max(boxes.stride(0), 4)
+        lds = scores.stride(0) if K > 1 else max(scores.stride(0), C)
+        L = int(G) if group is not None else C
+        if out is None:
+            dev = boxes.device
+            out = (torch.empty(B, max_num, 5, dtype=f32, device=dev), torch.empty(B, max_num, dtype=i32, device=dev),
+                   torch.empty(B, max_num, dtype=i32, device=dev), torch.empty(B, dtype=i32, device=dev))
+        dets, labels, inds, counts = out
+        assert all(t.is_contiguous() for t in out) and dets.dtype == f32 and labels.dtype == i32 and inds.dtype == i32 and counts.dtype == i32
+        assert dets.numel() == B * max_num * 5 and labels.numel() == B * max_num and inds.numel() == B * max_num and counts.numel() == B
+        if workspace is None:
+            need = self.nms_workspace(B, Kmax, L, max_num)
+            key = (B, int(Kmax), L, int(max_num), boxes.device)
+            cache = self.__dict__.setdefault("_nms_ws", {})
+            workspace = cache.get(key)
+            if workspace is None and need > 0:
+                workspace = cache[key] = torch.empty(need, dtype=torch.uint8, device=boxes.device)
+        self._ok(self.lib.csd_nms(_p(boxes), ldb, _p(scores), lds, C, _p(starts), _p(group), int(G), K, B, int(Kmax), float(score_thr),
+                                  float(iou_thr), int(max_num), _p(dets), _p(labels), _p(inds), _p(counts), _p(workspace), self._stream()),
+                 "csd_nms")
+        return dets, labels, inds, counts
+
+    def delta2bbox(self, rois, deltas, out, means=(0.0, 0.0, 0.0, 0.0), stds=(1.0, 1.0, 1.0, 1.0), wh_ratio_clip=16 / 1000, starts=None,
+                   max_shape=None, scale=None):
+        """mmdet's DeltaXYWHBBoxCoder.decode and the rescale (csd_delta2bbox): rois [K, 4] columns x0, y0, x1, y1 (a view rois[:, 1:] of
+        [K, 5] rois is fine), deltas [K, 4] -> out [K, 4].  max_shape [B, 2] = (h, w) and scale [B, 4] (the scale factors the boxes are
+        divided by) are device tensors per image and need starts [B + 1]."""
+        self._chk(rois, deltas, out, starts, max_shape, scale)
+        f32 = torch.float32
+        K = rois.shape[0]
+        for t in (rois, deltas, out):
+            assert t.dtype == f32 and t.dim() == 2 and t.shape == (K, 4) and (K == 0 or t.stride(1) == 1)
+        B = 0
+        if max_shape is not None or scale is not None:
+            assert starts is not None and starts.dtype == torch.int32 and starts.is_contiguous()
+            B = starts.numel() - 1
+            assert max_shape is None or (max_shape.dtype == f32 and max_shape.is_contiguous() and tuple(max_shape.shape) == (B, 2))
+            assert scale is None or (scale.dtype == f32 and scale.is_contiguous() and tuple(scale.shape) == (B, 4))
+        ld = lambda t: t.stride(0) if K > 1 else max(t.stride(0), 4)
+        m4, s4 = (_f * 4)(*[float(v) for v in means]), (_f * 4)(*[float(v) for v in stds])
+        self._ok(self.lib.csd_delta2bbox(_p(rois), ld(rois), _p(deltas), ld(deltas), _p(starts), B, K, m4, s4, float(wh_ratio_clip),
+                                         _p(max_shape), _p(scale), _p(out), ld(out), self._stream()), "csd_delta2bbox")
+        return out
 
     def roialign_bwd(self, dpooled, rois, dfeat, grid_h, grid_w, tok_off):
         self._chk(dpooled, rois, dfeat)

@@ -7,8 +7,9 @@
             with the detector's softmax as det^(1-alpha) * vlm^alpha on base classes and det^(1-beta) * vlm^beta on novel classes;
   :290-347 (FViTTransferBBoxHead)  the same with one exponent for all classes (seen_classes=None here).
 
-The convolutions and linears in front of `cls_score` (ConvFCBBoxHead), FPN, RPN and NMS are mmdet's and stay there: this module takes the
-class branch's output and the backbone's dense map (fvit.EvaCLIPViT's fifth output) and returns the blended scores [K, C].
+The convolutions and linears in front of `cls_score` (ConvFCBBoxHead), FPN and RPN are mmdet's and stay there: this module takes the
+class branch's output and the backbone's dense map (fvit.EvaCLIPViT's fifth output) and returns the blended scores [K, C].  `get_bboxes`
+(:123-164) turns them into detections through det_post (box decoding, class-aware NMS and the cut as HIP kernels, no mmcv / mmdet).
 
 Two routes.  FUSED (a kernel backend with BOX_SCORES, HipOps): one launch per call (cs_roialign_fwd's scoring form) that
 reads the tower's token-major map in place -- the NCHW tensor forward_intermediates returns is a permuted view of it, no copy is made --
@@ -73,8 +74,11 @@ class OpenVocabBoxScores(nn.Module):
     the kernel."""
 
     def __init__(self, class_embed, seen_classes=None, all_classes=None, vlm_temperature=100.0, alpha=0.2, beta=0.45, fixed_temperature=0,
-                 learned_temperature=50.0, learn_bg=False, featmap_stride=16, ops=None, fused=None):
+                 learned_temperature=50.0, learn_bg=False, featmap_stride=16, ops=None, fused=None, target_means=(0., 0., 0., 0.),
+                 target_stds=(0.1, 0.1, 0.2, 0.2), reg_class_agnostic=True):
         super().__init__()
+        # the bbox_coder of every F-ViT config: DeltaXYWHBBoxCoder(target_means, target_stds), class-agnostic regression
+        self.target_means, self.target_stds, self.reg_class_agnostic = tuple(target_means), tuple(target_stds), bool(reg_class_agnostic)
         assert class_embed is not None, "class embed is None"
         if fixed_temperature != 0:                                                     # fvit_head.py:27-31
             self.detect_temperature = fixed_temperature
@@ -213,6 +217,29 @@ class OpenVocabBoxScores(nn.Module):
             det = cls_score.detach().float().softmax(dim=-1)                           # :112
             w = self.exponents(det.device)
             return det ** (1 - w) * vlm ** w                                           # :116-119
+
+    # -------------------------------------------------------------------------------------------- detections
+    def get_bboxes(self, rois, cls_score, bbox_pred, img_shape, scale_factor, rescale=False, cfg=None):
+        """fvit_head.py:123-164 for one image, line for line, on det_post: rois [n, 5], cls_score [n, C + 1] (forward's scores; the
+        background column is last), bbox_pred [n, 4] or None, img_shape (h, w[, c]) or None, scale_factor 4 numbers (or one).
+        cfg None -> (bboxes, scores); cfg with score_thr, nms, max_per_img -> (det_bboxes [m, 5], det_labels [m]).  The batched,
+        fixed-shape, read-back-free form of the same is det_post.detections."""
+        from . import det_post
+        if self.training:                                                              # :136-140 (no custom_cls_channels loss here)
+            scores = F.softmax(cls_score, dim=-1) if cls_score is not None else None
+        else:
+            scores = cls_score
+        if bbox_pred is not None:                                                      # :143-146
+            bboxes = det_post.delta2bbox(rois[..., 1:], bbox_pred, self.target_means, self.target_stds, max_shape=img_shape)
+        else:
+            bboxes = rois[:, 1:].clone()                                               # :148-151: the reference's clamp_ acts on a copy
+        if rescale and bboxes.size(0) > 0:                                             # :153-156
+            sf = bboxes.new_tensor(scale_factor)
+            bboxes = (bboxes.view(bboxes.size(0), -1, 4) / sf).view(bboxes.size()[0], -1)
+        if cfg is None:                                                                # :158-164
+            return bboxes, scores
+        get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
+        return det_post.multiclass_nms(bboxes, scores, get("score_thr"), get("nms"), get("max_per_img"))
 
 
 try:                                                      # optional: the reference registers its heads with mmdet (fvit_head.py:13)
