@@ -87,6 +87,19 @@ DET_SIGNATURES = {
 }
 
 
+class RoiLevel(ctypes.Structure):
+    """include/clipself_roi.h: csr_level, one level of the RoI extractor's maps."""
+    _fields_ = [("map", _vp), ("ld", _l), ("h", _i), ("w", _i), ("spatial_scale", _f)]
+
+
+# include/clipself_roi.h: the detector's multi-level RoIAlign, forward and backward.  A third header, a third table
+ROI_SIGNATURES = {
+    "csr_roi_extract_workspace": (_sz, [_i]),
+    "csr_roi_extract_fwd": (_i, [ctypes.POINTER(RoiLevel), _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _l, _vp]),
+    "csr_roi_extract_bwd": (_i, [_vp, _l, _vp, _i, _i, _i, _f, ctypes.POINTER(RoiLevel), _i, _i, _i, _vp, _vp]),
+}
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -116,7 +129,7 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for table in (SIGNATURES, DET_SIGNATURES):
+        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -153,6 +166,7 @@ class HipOps:
     TOKEN_TAPS = True                   # tokens_to_nchw: the residual stream after a block as a [B, C, h, w] map (encode_dense(taps=), the detector backbone)
     DECONV_ROWS = True                  # rows_to_nchw / nchw_to_rows: 2x2 transposed convolutions as GEMMs on token rows (neck.Deconv2x2)
     DET_POST = True                     # nms / delta2bbox: box decoding, class-aware NMS and the per-image cut on the device (det_post)
+    ROI_EXTRACT = True                  # roi_extract_fwd / roi_extract_bwd: multi-level RoIAlign on channel-last maps, atomic-free backward (roi_extractor)
     BOX_SCORES = True                   # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -789,6 +803,68 @@ class HipOps:
         self._ok(self.lib.csd_delta2bbox(_p(rois), ld(rois), _p(deltas), ld(deltas), _p(starts), B, K, m4, s4, float(wh_ratio_clip),
                                          _p(max_shape), _p(scale), _p(out), ld(out), self._stream()), "csd_delta2bbox")
         return out
+
+    # -- detector RoI extractor (include/clipself_roi.h) -------------------------------------------------
+    def roi_extract_workspace(self, K) -> int:
+        return int(self.lib.csr_roi_extract_workspace(int(K)))
+
+    def _roi_levels(self, maps, grids, scales, B):
+        """maps[l]: the level's channel-last map as a 2-D view [B * h_l * w_l, C] (row = one cell, last stride 1, its own row stride);
+        grids[l] = (h_l, w_l); scales[l] = 1 / stride_l.  -> (csr_level array, L, C).  Limits are the library's to refuse."""
+        L = len(maps)
+        if not (len(grids) == L and len(scales) == L and L >= 1):
+            raise ValueError(f"roi_extract: {L} maps, {len(grids)} grids and {len(scales)} scales")
+        C = maps[0].shape[1]
+        arr = (RoiLevel * L)()
+        for l, (m, (h, w), s) in enumerate(zip(maps, grids, scales)):
+            if m.dtype != torch.float32 or m.dim() != 2:
+                raise ValueError(f"roi_extract: level {l} must be a 2-D fp32 view [B * h * w, C], got {m.dtype} {tuple(m.shape)}")
+            if tuple(m.shape) != (B * int(h) * int(w), C) or (m.shape[0] > 0 and m.stride(1) != 1):
+                raise ValueError(f"roi_extract: level {l} is {tuple(m.shape)} with strides {m.stride()}, expected [{B} * {h} * {w}, {C}] with last stride 1")
+            ld = m.stride(0) if m.shape[0] > 1 else max(m.stride(0), C)
+            arr[l] = RoiLevel(m.data_ptr(), ld, int(h), int(w), float(s))      # 1.0 / stride in double; the c_float field rounds it once
+        return arr, L, C
+
+    @staticmethod
+    def _roi_rows(t, K, P, C, who):
+        if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (K * P * P, C) or (t.shape[0] > 0 and t.stride(1) != 1):
+            raise ValueError(f"roi_extract: {who} must be a 2-D fp32 view [K * P * P, C] = [{K * P * P}, {C}] with last stride 1, "
+                             f"got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), C)
+
+    def roi_extract_fwd(self, maps, grids, scales, rois, out, B, P, sampling_ratio=0, finest_scale=56.0):
+        """Multi-level RoIAlign (csr_roi_extract_fwd): rois [K, 5] fp32 (image, x0, y0, x1, y1) -> out, the [K, P, P, C] bins as a 2-D
+        view [K * P * P, C].  maps / grids / scales: see _roi_levels; scales[l] = (float)(1 / stride_l)."""
+        self._chk(rois, out, *maps)
+        K = rois.shape[0]
+        if rois.dtype != torch.float32 or tuple(rois.shape) != (K, 5) or not rois.is_contiguous():
+            raise ValueError(f"roi_extract: rois must be contiguous fp32 [K, 5], got {rois.dtype} {tuple(rois.shape)}")
+        arr, L, C = self._roi_levels(maps, grids, scales, B)
+        ldo = self._roi_rows(out, K, P, C, "out")
+        self._ok(self.lib.csr_roi_extract_fwd(arr, L, int(B), C, _p(rois), K, int(P), int(sampling_ratio), float(finest_scale), _p(out), ldo,
+                                              self._stream()), "csr_roi_extract_fwd")
+        return out
+
+    def roi_extract_bwd(self, dout, rois, dmaps, grids, scales, B, P, sampling_ratio=0, finest_scale=56.0, workspace=None):
+        """dmaps[l] += the gradient of roi_extract_fwd's out with respect to level l, all levels in one call (csr_roi_extract_bwd): a
+        gather in ascending box row, no floating-point atomics, equal bits from equal inputs.  The workspace is cached per K (pass
+        workspace= to own it); calls that share a K must share a stream."""
+        self._chk(rois, dout, workspace, *dmaps)
+        K = rois.shape[0]
+        if rois.dtype != torch.float32 or tuple(rois.shape) != (K, 5) or not rois.is_contiguous():
+            raise ValueError(f"roi_extract: rois must be contiguous fp32 [K, 5], got {rois.dtype} {tuple(rois.shape)}")
+        arr, L, C = self._roi_levels(dmaps, grids, scales, B)
+        ldo = self._roi_rows(dout, K, P, C, "dout")
+        if workspace is None:
+            need = self.roi_extract_workspace(K)
+            cache = self.__dict__.setdefault("_roi_ws", {})
+            key = (K, rois.device)
+            workspace = cache.get(key)
+            if workspace is None and need > 0:
+                workspace = cache[key] = torch.empty(need, dtype=torch.uint8, device=rois.device)
+        self._ok(self.lib.csr_roi_extract_bwd(_p(dout), ldo, _p(rois), K, int(P), int(sampling_ratio), float(finest_scale), arr, L, int(B), C,
+                                              _p(workspace), self._stream()), "csr_roi_extract_bwd")
+        return dmaps
 
     def roialign_bwd(self, dpooled, rois, dfeat, grid_h, grid_w, tok_off):
         self._chk(dpooled, rois, dfeat)
