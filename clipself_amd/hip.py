@@ -100,6 +100,17 @@ ROI_SIGNATURES = {
 }
 
 
+# include/clipself_assign.h: the detector's training targets (IoU assignment, sampling, box deltas).  A fourth header, a fourth table
+_f4 = ctypes.POINTER(_f)
+ASSIGN_SIGNATURES = {
+    "csa_workspace": (_sz, [_i, _i, _i, _i]),
+    "csa_assign": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _i, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "csa_sample": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "csa_targets": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f4, _f4, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+ASSIGN_MAX_ROWS, ASSIGN_MAX_GT, ASSIGN_MAX_NUM = 1 << 20, 1024, 4096       # include/clipself_assign.h: Nmax, Gmax, num
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -129,7 +140,7 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES):
+        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -167,7 +178,8 @@ class HipOps:
     DECONV_ROWS = True                  # rows_to_nchw / nchw_to_rows: 2x2 transposed convolutions as GEMMs on token rows (neck.Deconv2x2)
     DET_POST = True                     # nms / delta2bbox: box decoding, class-aware NMS and the per-image cut on the device (det_post)
     ROI_EXTRACT = True                  # roi_extract_fwd / roi_extract_bwd: multi-level RoIAlign on channel-last maps, atomic-free backward (roi_extractor)
-    BOX_SCORES = True                   # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
+    ASSIGN = True                       # assign / sample / bbox_targets: IoU assignment, random sampling and box-delta targets on the device (det_targets)
+    BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
         self.lib = load_library()
@@ -803,6 +815,131 @@ class HipOps:
         self._ok(self.lib.csd_delta2bbox(_p(rois), ld(rois), _p(deltas), ld(deltas), _p(starts), B, K, m4, s4, float(wh_ratio_clip),
                                          _p(max_shape), _p(scale), _p(out), ld(out), self._stream()), "csd_delta2bbox")
         return out
+
+    # -- detector training targets (include/clipself_assign.h) -----------------------------------------
+    def assign_workspace(self, B, Nmax, Gmax, num=1) -> int:
+        return int(self.lib.csa_workspace(int(B), int(Nmax), int(Gmax), int(num)))
+
+    @staticmethod
+    def _assign_layout(boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax):
+        """The checks the three csa_ wrappers share -> (K, ldb, Gtot, ldg).  ValueError, not assert: these are user-facing limits."""
+        f32, i32 = torch.float32, torch.int32
+        if boxes.dtype != f32 or boxes.dim() != 2 or boxes.shape[1] != 4 or (boxes.shape[0] and boxes.stride(1) != 1):
+            raise ValueError(f"boxes must be fp32 [K, 4] with last stride 1, got {boxes.dtype} {tuple(boxes.shape)} strides {boxes.stride()}")
+        if gt_boxes.dtype != f32 or gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4 or (gt_boxes.shape[0] and gt_boxes.stride(1) != 1):
+            raise ValueError(f"gt_boxes must be fp32 [Gtot, 4] with last stride 1, got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
+        if gt_starts.dtype != i32 or not gt_starts.is_contiguous() or gt_starts.numel() != B + 1:
+            raise ValueError(f"gt_starts must be contiguous int32 [B + 1] = [{B + 1}], got {gt_starts.dtype} {tuple(gt_starts.shape)}")
+        if starts is not None and (starts.dtype != i32 or not starts.is_contiguous() or starts.numel() != B + 1):
+            raise ValueError(f"starts must be None (shared rows) or contiguous int32 [B + 1] = [{B + 1}], got {starts.dtype} {tuple(starts.shape)}")
+        if not (1 <= B <= 65535 and 0 <= Nmax <= ASSIGN_MAX_ROWS and 0 <= Gmax <= ASSIGN_MAX_GT):
+            raise ValueError(f"limits: 1 <= B <= 65535, 0 <= Nmax <= {ASSIGN_MAX_ROWS}, 0 <= Gmax <= {ASSIGN_MAX_GT} (B = {B}, Nmax = {Nmax}, Gmax = {Gmax})")
+        K, Gtot = boxes.shape[0], gt_boxes.shape[0]
+        return K, (boxes.stride(0) if K > 1 else max(boxes.stride(0), 4)), Gtot, (gt_boxes.stride(0) if Gtot > 1 else max(gt_boxes.stride(0), 4))
+
+    def assign(self, boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax, pos_iou_thr, neg_iou_thr, min_pos_iou=0.0, match_low_quality=True,
+               gt_max_assign_all=True, gt_prefix=False, valid=None, out=None, workspace=None):
+        """MaxIoUAssigner.assign for B images in one call (csa_assign): boxes [K, 4] grouped by starts [B + 1] int32 (None: all images share
+        the K rows), gt_boxes [Gtot, 4] grouped by gt_starts, valid [K] uint8 or None; neg_iou_thr a float or (lo, hi).
+        -> (gt_inds [B, Nmax] int32, max_overlaps [B, Nmax] fp32); nothing is read back.  The workspace is cached per shape."""
+        self._chk(boxes, starts, gt_boxes, gt_starts, valid, workspace)
+        B, Nmax, Gmax = int(B), int(Nmax), int(Gmax)
+        K, ldb, Gtot, ldg = self._assign_layout(boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax)
+        if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or valid.numel() != K):
+            raise ValueError(f"valid must be contiguous uint8 [K] = [{K}], got {valid.dtype} {tuple(valid.shape)}")
+        lo, hi = (neg_iou_thr if isinstance(neg_iou_thr, (tuple, list)) else (0.0, neg_iou_thr))
+        if out is None:
+            out = (torch.empty(B, Nmax, dtype=torch.int32, device=boxes.device), torch.empty(B, Nmax, dtype=torch.float32, device=boxes.device))
+        gt_inds, max_overlaps = out
+        if not (gt_inds.dtype == torch.int32 and max_overlaps.dtype == torch.float32 and gt_inds.is_contiguous() and max_overlaps.is_contiguous()
+                and gt_inds.numel() == B * Nmax and max_overlaps.numel() == B * Nmax):
+            raise ValueError("out must be (int32 [B, Nmax], fp32 [B, Nmax]), contiguous")
+        if workspace is None:
+            key = (B, Gmax, boxes.device)
+            cache = self.__dict__.setdefault("_assign_ws", {})
+            workspace = cache.get(key)
+            if workspace is None:
+                workspace = cache[key] = torch.empty(self.assign_workspace(B, Nmax, Gmax), dtype=torch.uint8, device=boxes.device)
+        self._ok(self.lib.csa_assign(_p(boxes), ldb, _p(starts), K, _p(gt_boxes), ldg, _p(gt_starts), Gtot, _p(valid), B, Nmax, Gmax,
+                                     float(pos_iou_thr), float(lo), float(hi), float(min_pos_iou), int(bool(match_low_quality)),
+                                     int(bool(gt_max_assign_all)), int(bool(gt_prefix)), _p(gt_inds), _p(max_overlaps), _p(workspace),
+                                     self._stream()), "csa_assign")
+        return gt_inds, max_overlaps
+
+    def sample(self, gt_inds, keys, starts, K, gt_starts, Gtot, Gmax, num, expected_pos, neg_pos_ub=-1.0, out=None):
+        """RandomSampler.sample for B images (csa_sample): gt_inds [B, Nmax] int32, keys [B, Nmax] uint32 bits (int32 or uint32 tensor).
+        -> (flags [B, Nmax] uint8, sel [B, num] int32, counts [B, 2] int32); nothing is read back."""
+        self._chk(gt_inds, keys, starts, gt_starts)
+        if gt_inds.dim() != 2 or gt_inds.dtype != torch.int32 or not gt_inds.is_contiguous():
+            raise ValueError(f"gt_inds must be contiguous int32 [B, Nmax], got {gt_inds.dtype} {tuple(gt_inds.shape)}")
+        B, Nmax = gt_inds.shape
+        if keys.element_size() != 4 or keys.is_floating_point() or not keys.is_contiguous() or tuple(keys.shape) != (B, Nmax):
+            raise ValueError(f"keys must be contiguous 32-bit integers [B, Nmax] = [{B}, {Nmax}], got {keys.dtype} {tuple(keys.shape)}")
+        num, expected_pos, Gmax = int(num), int(expected_pos), int(Gmax)
+        if not (1 <= B <= 65535 and 0 <= Nmax <= ASSIGN_MAX_ROWS and 0 <= Gmax <= ASSIGN_MAX_GT and 1 <= num <= ASSIGN_MAX_NUM and 0 <= expected_pos <= num):
+            raise ValueError(f"limits: 1 <= B <= 65535, Nmax <= {ASSIGN_MAX_ROWS}, Gmax <= {ASSIGN_MAX_GT}, 1 <= num <= {ASSIGN_MAX_NUM}, "
+                             f"0 <= expected_pos <= num (B = {B}, Nmax = {Nmax}, Gmax = {Gmax}, num = {num}, expected_pos = {expected_pos})")
+        for t, who in ((starts, "starts"), (gt_starts, "gt_starts")):
+            if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != B + 1):
+                raise ValueError(f"{who} must be contiguous int32 [B + 1] = [{B + 1}]")
+        if gt_starts is None:
+            raise ValueError("gt_starts is needed (gt_inds is checked against each image's ground-truth count)")
+        if out is None:
+            dev = gt_inds.device
+            out = (torch.empty(B, Nmax, dtype=torch.uint8, device=dev), torch.empty(B, num, dtype=torch.int32, device=dev),
+                   torch.empty(B, 2, dtype=torch.int32, device=dev))
+        flags, sel, counts = out
+        if not (flags.dtype == torch.uint8 and sel.dtype == torch.int32 and counts.dtype == torch.int32 and all(t.is_contiguous() for t in out)
+                and flags.numel() == B * Nmax and sel.numel() == B * num and counts.numel() == 2 * B):
+            raise ValueError("out must be (uint8 [B, Nmax], int32 [B, num], int32 [B, 2]), contiguous")
+        self._ok(self.lib.csa_sample(_p(gt_inds), _p(keys), _p(starts), int(K), _p(gt_starts), int(Gtot), B, Nmax, Gmax, num, expected_pos,
+                                     float(neg_pos_ub), _p(flags), _p(sel), _p(counts), self._stream()), "csa_sample")
+        return flags, sel, counts
+
+    def bbox_targets(self, boxes, starts, gt_boxes, gt_labels, gt_starts, Gmax, gt_inds, flags=None, sel=None, means=(0.0, 0.0, 0.0, 0.0),
+                     stds=(1.0, 1.0, 1.0, 1.0), bg_label=1, pos_weight=-1.0, out=None):
+        """Labels, weights and bbox2delta targets (csa_targets).  out: the outputs, in the order returned, to own them.  sel None: the dense form of the anchor head, from flags [B, Nmax] ->
+        (labels [B, Nmax], label_weights [B, Nmax], bbox_targets [B, Nmax, 4], bbox_weights [B, Nmax, 4]).  sel [B, num]: the compact form
+        of the box head -> (rois [B, num, 5], labels [B, num], label_weights [B, num], bbox_targets [B, num, 4], bbox_weights [B, num, 4])."""
+        self._chk(boxes, starts, gt_boxes, gt_labels, gt_starts, gt_inds, flags, sel)
+        if gt_inds.dim() != 2 or gt_inds.dtype != torch.int32 or not gt_inds.is_contiguous():
+            raise ValueError(f"gt_inds must be contiguous int32 [B, Nmax], got {gt_inds.dtype} {tuple(gt_inds.shape)}")
+        B, Nmax = gt_inds.shape
+        Gmax = int(Gmax)
+        K, ldb, Gtot, ldg = self._assign_layout(boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax)
+        if gt_labels is not None and (gt_labels.dtype != torch.int32 or not gt_labels.is_contiguous() or gt_labels.numel() != Gtot):
+            raise ValueError(f"gt_labels must be contiguous int32 [Gtot] = [{Gtot}], got {gt_labels.dtype} {tuple(gt_labels.shape)}")
+        if pos_weight > 0:
+            raise ValueError(f"pos_weight = {pos_weight} is not supported (only pos_weight <= 0)")
+        dev, f32, i32 = boxes.device, torch.float32, torch.int32
+        num, rois = 1, None
+        if sel is None:
+            if flags is None or flags.dtype != torch.uint8 or not flags.is_contiguous() or tuple(flags.shape) != (B, Nmax):
+                raise ValueError(f"the dense form needs flags: contiguous uint8 [B, Nmax] = [{B}, {Nmax}]")
+            S = Nmax
+        else:
+            if sel.dtype != i32 or sel.dim() != 2 or not sel.is_contiguous() or sel.shape[0] != B or not 1 <= sel.shape[1] <= ASSIGN_MAX_NUM:
+                raise ValueError(f"sel must be contiguous int32 [B, num] with 1 <= num <= {ASSIGN_MAX_NUM}, got {sel.dtype} {tuple(sel.shape)}")
+            S = num = sel.shape[1]
+        if out is None:
+            out = (torch.empty(B, S, dtype=i32, device=dev), torch.empty(B, S, dtype=f32, device=dev),
+                   torch.empty(B, S, 4, dtype=f32, device=dev), torch.empty(B, S, 4, dtype=f32, device=dev))
+            if sel is not None:
+                out = (torch.empty(B, S, 5, dtype=f32, device=dev),) + out
+        if len(out) != (4 if sel is None else 5):
+            raise ValueError("out must hold (labels, label_weights, bbox_targets, bbox_weights), with rois in front in the compact form")
+        if sel is not None:
+            rois = out[0]
+        labels, label_weights, bt, bw = out[-4:]
+        want = [(labels, i32, B * S), (label_weights, f32, B * S), (bt, f32, B * S * 4), (bw, f32, B * S * 4)] + ([(rois, f32, B * S * 5)] if sel is not None else [])
+        for t, dt, n in want:
+            if t.dtype != dt or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
+                raise ValueError(f"out: expected a contiguous {dt} device tensor of {n} elements, got {t.dtype} {tuple(t.shape)}")
+        m4, s4 = (_f * 4)(*[float(v) for v in means]), (_f * 4)(*[float(v) for v in stds])
+        self._ok(self.lib.csa_targets(_p(boxes), ldb, _p(starts), K, _p(gt_boxes), ldg, _p(gt_labels), _p(gt_starts), Gtot, B, Nmax, Gmax,
+                                      _p(gt_inds), _p(flags), _p(sel), num, m4, s4, int(bg_label), float(pos_weight), _p(rois), _p(labels),
+                                      _p(label_weights), _p(bt), _p(bw), self._stream()), "csa_targets")
+        return (labels, label_weights, bt, bw) if sel is None else (rois, labels, label_weights, bt, bw)
 
     # -- detector RoI extractor (include/clipself_roi.h) -------------------------------------------------
     def roi_extract_workspace(self, K) -> int:
