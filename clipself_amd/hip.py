@@ -111,6 +111,20 @@ ASSIGN_SIGNATURES = {
 ASSIGN_MAX_ROWS, ASSIGN_MAX_GT, ASSIGN_MAX_NUM = 1 << 20, 1024, 4096       # include/clipself_assign.h: Nmax, Gmax, num
 
 
+class LossLevel(ctypes.Structure):
+    """include/clipself_loss.h: csl_level, one level of the RPN's predictions and their gradients."""
+    _fields_ = [("cls", _vp), ("reg", _vp), ("dcls", _vp), ("dreg", _vp), ("h", _i), ("w", _i)]
+
+
+# include/clipself_loss.h: the detector's losses with their gradients (RPN and box head).  A fifth header, a fifth table
+LOSS_SIGNATURES = {
+    "csl_workspace": (_sz, [ctypes.POINTER(LossLevel), _i, _i, _i, _i]),
+    "csl_rpn_loss": (_i, [ctypes.POINTER(LossLevel), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csl_bbox_head_loss": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_SIDE, LOSS_MAX_ROWS, LOSS_MAX_CLASSES = 8, 16, 512, 1 << 20, 4096    # include/clipself_loss.h
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -140,7 +154,7 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES):
+        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -179,6 +193,7 @@ class HipOps:
     DET_POST = True                     # nms / delta2bbox: box decoding, class-aware NMS and the per-image cut on the device (det_post)
     ROI_EXTRACT = True                  # roi_extract_fwd / roi_extract_bwd: multi-level RoIAlign on channel-last maps, atomic-free backward (roi_extractor)
     ASSIGN = True                       # assign / sample / bbox_targets: IoU assignment, random sampling and box-delta targets on the device (det_targets)
+    LOSS = True                         # rpn_loss / bbox_head_loss: the RPN's and the box head's losses with their gradients, one call per head (det_losses)
     BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -940,6 +955,117 @@ class HipOps:
                                       _p(gt_inds), _p(flags), _p(sel), num, m4, s4, int(bg_label), float(pos_weight), _p(rois), _p(labels),
                                       _p(label_weights), _p(bt), _p(bw), self._stream()), "csa_targets")
         return (labels, label_weights, bt, bw) if sel is None else (rois, labels, label_weights, bt, bw)
+
+    # -- detector losses (include/clipself_loss.h) ------------------------------------------------------
+    @staticmethod
+    def _loss_dense(t, dtype, shape, who):
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{who} must be a contiguous {dtype} device tensor {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+    def _loss_levels(self, cls_scores, bbox_preds, dcls=None, dreg=None):
+        L = len(cls_scores)
+        if not (1 <= L <= LOSS_MAX_LEVELS and len(bbox_preds) == L):
+            raise ValueError(f"rpn_loss: {L} cls maps and {len(bbox_preds)} reg maps (1 <= L <= {LOSS_MAX_LEVELS})")
+        B, A = cls_scores[0].shape[0], cls_scores[0].shape[1]
+        arr, N = (LossLevel * L)(), 0
+        for l, (c, r) in enumerate(zip(cls_scores, bbox_preds)):
+            if c.dim() != 4:
+                raise ValueError(f"rpn_loss: level {l}: cls must be [B, A, h, w], got {tuple(c.shape)}")
+            h, w = c.shape[2], c.shape[3]
+            self._loss_dense(c, torch.float32, (B, A, h, w), f"rpn_loss: level {l}: cls")
+            self._loss_dense(r, torch.float32, (B, 4 * A, h, w), f"rpn_loss: level {l}: reg")
+            if dcls is not None:
+                self._loss_dense(dcls[l], torch.float32, (B, A, h, w), f"rpn_loss: level {l}: dcls")
+                self._loss_dense(dreg[l], torch.float32, (B, 4 * A, h, w), f"rpn_loss: level {l}: dreg")
+            arr[l] = LossLevel(c.data_ptr(), r.data_ptr(), None if dcls is None else dcls[l].data_ptr(), None if dreg is None else dreg[l].data_ptr(),
+                               int(h), int(w))
+            N += h * w * A
+        return arr, L, B, A, N
+
+    def loss_workspace(self, cls_scores=None, bbox_preds=None, R=0) -> int:
+        """Bytes of workspace (csl_workspace) for rpn_loss on these maps and / or bbox_head_loss on R rows; 0 outside the limits."""
+        if cls_scores is None:
+            return int(self.lib.csl_workspace(None, 0, 1, 1, int(R)))
+        arr, L, B, A, _ = self._loss_levels(cls_scores, bbox_preds)
+        return int(self.lib.csl_workspace(arr, L, B, A, int(R)))
+
+    def _loss_ws(self, need, device, workspace):
+        if need <= 0:
+            raise ValueError("the shapes are outside the limits of include/clipself_loss.h")
+        if workspace is None:
+            cache = self.__dict__.setdefault("_loss_ws_cache", {})
+            workspace = cache.get(device)
+            if workspace is None or workspace.numel() < need:
+                workspace = cache[device] = torch.empty(need, dtype=torch.uint8, device=device)
+        if workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace holds {workspace.numel() * workspace.element_size()} bytes, {need} are needed")
+        return workspace
+
+    def rpn_loss(self, cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factor, grad=True, out=None, workspace=None):
+        """RPNHead.loss for all levels and images in one call (csl_rpn_loss).  cls_scores[l] [B, A, h, w], bbox_preds[l] [B, 4A, h, w];
+        the dense targets [B, N] / [B, N, 4] as bbox_targets' dense form returns them; avg_factor a device fp32 scalar.
+        -> (losses [L, 2], dcls list, dreg list), the gradient lists None with grad=False.  out: the same triple, to own the outputs.
+        The workspace is cached per device (pass workspace= to own it); calls that share it must share a stream."""
+        self._chk(labels, label_weights, bbox_targets, bbox_weights, avg_factor, *cls_scores, *bbox_preds)
+        dev = labels.device
+        if out is None:
+            losses = torch.empty(len(cls_scores), 2, dtype=torch.float32, device=dev)
+            dcls = [torch.empty_like(c) for c in cls_scores] if grad else None
+            dreg = [torch.empty_like(r) for r in bbox_preds] if grad else None
+        else:
+            losses, dcls, dreg = out
+        if (dcls is None) != (dreg is None):
+            raise ValueError("rpn_loss: dcls and dreg are given together or both None")
+        arr, L, B, A, N = self._loss_levels(cls_scores, bbox_preds, dcls, dreg)
+        self._loss_dense(labels, torch.int32, (B, N), "rpn_loss: labels")
+        self._loss_dense(label_weights, torch.float32, (B, N), "rpn_loss: label_weights")
+        self._loss_dense(bbox_targets, torch.float32, (B, N, 4), "rpn_loss: bbox_targets")
+        self._loss_dense(bbox_weights, torch.float32, (B, N, 4), "rpn_loss: bbox_weights")
+        self._loss_dense(losses, torch.float32, (L, 2), "rpn_loss: losses")
+        if avg_factor.dtype != torch.float32 or avg_factor.numel() != 1:
+            raise ValueError(f"rpn_loss: avg_factor must be a device fp32 scalar, got {avg_factor.dtype} {tuple(avg_factor.shape)}")
+        ws = self._loss_ws(int(self.lib.csl_workspace(arr, L, B, A, 0)), dev, workspace)
+        self._ok(self.lib.csl_rpn_loss(arr, L, B, A, _p(labels), _p(label_weights), _p(bbox_targets), _p(bbox_weights), _p(avg_factor), _p(losses),
+                                       _p(ws), self._stream()), "csl_rpn_loss")
+        return losses, dcls, dreg
+
+    def bbox_head_loss(self, cls_score, labels, label_weights, bbox_pred, bbox_targets, bbox_weights, bg_label, class_weight=None, avg_factor=None,
+                       grad=True, out=None, workspace=None):
+        """BBoxHead.loss, class-agnostic boxes, CustomCrossEntropyLoss + L1Loss + accuracy in one call (csl_bbox_head_loss).  cls_score
+        [R, C1] fp32 with last stride 1 (its row stride is ldc); class_weight [C1] or None; avg_factor a device fp32 scalar or None
+        (None: max(count(label_weights > 0), 1) on the device).  -> (out4 = (loss_cls, acc, loss_bbox, avg) [4], dcls [R, C1] with
+        cls_score's row stride, dbbox [R, 4]), the gradients None with grad=False.  out: the same triple, to own the outputs."""
+        self._chk(cls_score, labels, label_weights, bbox_pred, bbox_targets, bbox_weights, class_weight, avg_factor)
+        if cls_score.dim() != 2 or cls_score.dtype != torch.float32 or (cls_score.numel() and cls_score.stride(1) != 1):
+            raise ValueError(f"bbox_head_loss: cls_score must be fp32 [R, C1] with last stride 1, got {cls_score.dtype} {tuple(cls_score.shape)}")
+        R, C1 = cls_score.shape
+        ldc = max(cls_score.stride(0), C1) if R > 0 else C1
+        dev, f32 = cls_score.device, torch.float32
+        self._loss_dense(labels, torch.int32, (R,), "bbox_head_loss: labels")
+        self._loss_dense(label_weights, f32, (R,), "bbox_head_loss: label_weights")
+        for t, who in ((bbox_pred, "bbox_pred"), (bbox_targets, "bbox_targets"), (bbox_weights, "bbox_weights")):
+            self._loss_dense(t, f32, (R, 4), "bbox_head_loss: " + who)
+        if class_weight is not None:
+            self._loss_dense(class_weight, f32, (C1,), "bbox_head_loss: class_weight")
+        if avg_factor is not None and (avg_factor.dtype != f32 or avg_factor.numel() != 1):
+            raise ValueError(f"bbox_head_loss: avg_factor must be a device fp32 scalar or None, got {avg_factor.dtype} {tuple(avg_factor.shape)}")
+        if out is None:
+            out4 = torch.empty(4, dtype=f32, device=dev)
+            dcls = torch.empty_strided((R, C1), (ldc, 1), dtype=f32, device=dev) if grad else None
+            dbbox = torch.empty(R, 4, dtype=f32, device=dev) if grad else None
+        else:
+            out4, dcls, dbbox = out
+        self._loss_dense(out4, f32, (4,), "bbox_head_loss: out")
+        if dcls is not None:
+            if dcls.dtype != f32 or tuple(dcls.shape) != (R, C1) or not dcls.is_cuda or (R > 0 and dcls.stride(1) != 1) or (R > 1 and dcls.stride(0) != ldc):
+                raise ValueError(f"bbox_head_loss: dcls must be fp32 [R, C1] with cls_score's strides ({ldc}, 1), got {tuple(dcls.shape)} {dcls.stride()}")
+        if dbbox is not None:
+            self._loss_dense(dbbox, f32, (R, 4), "bbox_head_loss: dbbox")
+        ws = self._loss_ws(int(self.lib.csl_workspace(None, 0, 1, 1, R)), dev, workspace)
+        self._ok(self.lib.csl_bbox_head_loss(_p(cls_score), ldc, _p(labels), _p(label_weights), _p(class_weight), _p(bbox_pred), _p(bbox_targets),
+                                             _p(bbox_weights), R, C1, int(bg_label), _p(avg_factor), _p(out4), _p(dcls), _p(dbbox), _p(ws),
+                                             self._stream()), "csl_bbox_head_loss")
+        return out4, dcls, dbbox
 
     # -- detector RoI extractor (include/clipself_roi.h) -------------------------------------------------
     def roi_extract_workspace(self, K) -> int:
