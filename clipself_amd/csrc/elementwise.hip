@@ -173,8 +173,10 @@ __device__ __forceinline__ float gelu_f(float x) {
 template <bool QUICK>
 __device__ __forceinline__ float gelu_grad_f(float x) {
     if (QUICK) {
+        // s + 1.702 x s (1 - s), the saturated factor s (1 - s) multiplied first: s * (1 + 1.702 x (1 - s)) is inf * 0 = NaN once 1.702 x
+        // overflows (finite bf16 |x| >= 2.007e38) while s is exactly 0 or 1.  Every finite input gives a finite gradient.
         const float s = 1.f / (1.f + __expf(-1.702f * x));
-        return s * (1.f + 1.702f * x * (1.f - s));
+        return s + 1.702f * (x * (s * (1.f - s)));
     }
     return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }

@@ -226,7 +226,9 @@ int cs_swiglu_bwd_q8(const void* dh, long lddh, const void* x12, long ldx, void*
                      int M, int Hd, cs_stream_t stream);
 
 /* --- GELU / QuickGELU elementwise on bf16 [M,N] (training path keeps the c_fc output): src/open_clip/transformer.py:31-34,211
- *     y = act(x); dx = dy * act'(x); quick 0 = nn.GELU (erf), 1 = x*sigmoid(1.702x) */
+ *     y = act(x); dx = dy * act'(x); quick 0 = nn.GELU (erf), 1 = x*sigmoid(1.702x).  Every finite bf16 x gives a finite y and, with a
+ *     finite dy whose product with act'(x) (|act'| < 1.13) is representable, a finite dx: no intermediate overflows, up to the largest
+ *     finite |x| (tests/_pointwise_ref.py runs all 65 280 finite inputs) */
 int cs_gelu_fwd(const void* x, long ldx, void* y, long ldy, int M, int N, int quick, cs_stream_t stream);
 int cs_gelu_bwd(const void* dy, long lddy, const void* x, long ldx, void* dx, long lddx, int M, int N, int quick, cs_stream_t stream);
 
