@@ -574,12 +574,32 @@ def rpn_targets(anchors, valid, gt_bboxes_list, assigner, sampler, coder_means=(
     return labels, lw, bt, bw, counts.sum().clamp(min=1)
 
 
+def _pos_gt_inds(gt_inds, sel, starts, gt_starts, K, Gtot, Gmax):
+    """[B * num] int32: the row of each slot's assigned ground truth in the concatenated ground-truth list, -1 for negatives and padding
+    slots.  One gather on the tensors' device, with the clamping of the header's starts / gt_starts; nothing is read back."""
+    dev, i64 = gt_inds.device, torch.int64
+    B, Nmax = gt_inds.shape
+    if Nmax == 0:
+        return torch.full((sel.numel(),), -1, dtype=torch.int32, device=dev)
+    st = torch.as_tensor(starts, device=dev).to(i64).clamp(0, K)
+    gst = torch.as_tensor(gt_starts, device=dev).to(i64).clamp(0, Gtot)
+    n = (st[1:] - st[:-1]).clamp(0, Nmax)
+    g = (gst[1:] - gst[:-1]).clamp(0, Gmax)
+    rows = sel.to(i64)
+    ok = (rows >= 0) & (rows < n[:, None])
+    gi = gt_inds.to(i64).gather(1, rows.clamp(0, Nmax - 1))
+    pos = ok & (gi > 0) & (gi <= g[:, None])
+    return torch.where(pos, gst[:-1, None] + gi - 1, torch.full_like(gi, -1)).to(torch.int32).reshape(-1)
+
+
 def rcnn_targets(proposals, gt_bboxes_list, gt_labels_list, assigner, sampler, coder_means=(0., 0., 0., 0.), coder_stds=(.1, .1, .2, .2),
-                 num_classes=65, generator=None, keys=None, ops=None):
+                 num_classes=65, generator=None, keys=None, ops=None, return_gt_inds=False):
     """StandardRoIHead's assign + sample and BBoxHead.get_targets (reg_class_agnostic=True) for all images, fixed shapes, no read-back on
     the kernel route.  proposals [B, P, 4] or a list of [P_b, 4(+)] tensors.
     -> rois [B * num, 5], labels [B * num] int32, label_weights [B * num], bbox_targets [B * num, 4], bbox_weights [B * num, 4]; slots a
-    sampler could not fill are rows with image -1 and zero weights, which SingleRoIExtractor pools to zeros."""
+    sampler could not fill are rows with image -1 and zero weights, which SingleRoIExtractor pools to zeros.
+    return_gt_inds=True adds a sixth tensor, pos_gt_inds [B * num] int32: the row of the slot's assigned ground truth in the concatenated
+    ground-truth list (what `det_masks.mask_target` indexes the masks with), -1 for negatives and padding slots."""
     props = [p[:, :4] for p in (proposals if isinstance(proposals, (list, tuple)) else proposals.unbind(0))]
     B, dev = len(props), props[0].device
     if len(gt_bboxes_list) != B or len(gt_labels_list) != B:
@@ -603,4 +623,7 @@ def rcnn_targets(proposals, gt_bboxes_list, gt_labels_list, assigner, sampler, c
     rois, lab, lw, bt, bw = bbox_targets(boxes, starts_t, gts, labels, gt_starts_t, Gmax, gt_inds, None, sel, coder_means, coder_stds,
                                          int(num_classes), -1.0, ops)
     n = B * sampler.num
-    return rois.reshape(n, 5), lab.reshape(n), lw.reshape(n), bt.reshape(n, 4), bw.reshape(n, 4)
+    out = (rois.reshape(n, 5), lab.reshape(n), lw.reshape(n), bt.reshape(n, 4), bw.reshape(n, 4))
+    if return_gt_inds:
+        out += (_pos_gt_inds(gt_inds, sel, starts_t, gt_starts_t, K, Gtot, Gmax),)
+    return out

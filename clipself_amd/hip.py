@@ -125,6 +125,16 @@ LOSS_SIGNATURES = {
 LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_SIDE, LOSS_MAX_ROWS, LOSS_MAX_CLASSES = 8, 16, 512, 1 << 20, 4096    # include/clipself_loss.h
 
 
+# include/clipself_mask.h: the detector's mask branch (mask targets, mask loss with gradient, mask paste).  A sixth header, a sixth table
+MASK_SIGNATURES = {
+    "csm_workspace": (_sz, [_i]),
+    "csm_mask_target": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _l, _l, _i, _i, _vp, _vp]),
+    "csm_mask_loss": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "csm_paste_masks": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+}
+MASK_MAX_ROWS, MASK_MAX_SIDE, MASK_MAX_MASK, MASK_MAX_CLASSES, MASK_MAX_IMAGE = 1 << 20, 2048, 64, 4096, 16384    # include/clipself_mask.h
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -154,7 +164,7 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES):
+        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES, MASK_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -194,6 +204,7 @@ class HipOps:
     ROI_EXTRACT = True                  # roi_extract_fwd / roi_extract_bwd: multi-level RoIAlign on channel-last maps, atomic-free backward (roi_extractor)
     ASSIGN = True                       # assign / sample / bbox_targets: IoU assignment, random sampling and box-delta targets on the device (det_targets)
     LOSS = True                         # rpn_loss / bbox_head_loss: the RPN's and the box head's losses with their gradients, one call per head (det_losses)
+    MASK = True                         # mask_target / mask_loss / paste_masks: the mask branch's targets, loss with gradient and paste (det_masks)
     BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -1066,6 +1077,90 @@ class HipOps:
                                              _p(bbox_weights), R, C1, int(bg_label), _p(avg_factor), _p(out4), _p(dcls), _p(dbbox), _p(ws),
                                              self._stream()), "csl_bbox_head_loss")
         return out4, dcls, dbbox
+
+    # -- detector mask branch (include/clipself_mask.h) --------------------------------------------------
+    def mask_workspace(self, R) -> int:
+        """Bytes of workspace (csm_workspace) for mask_loss on R rows; 0 outside the limits."""
+        return int(self.lib.csm_workspace(int(R)))
+
+    def mask_target(self, rois, gt_rows, masks, M, soft=False, out=None):
+        """mask_target / BitmapMasks.crop_and_resize (csm_mask_target).  rois [R, 5] fp32 contiguous (image, x0, y0, x1, y1), gt_rows [R]
+        int32 (rows outside [0, Gtot) give zero targets), masks [Gtot, H, W] uint8 with last stride 1 (its row and plane strides are
+        passed on).  -> targets [R, M, M], uint8 (t >= 0.5) or, with soft=True, fp32.  Nothing is read back."""
+        self._chk(rois, gt_rows, masks)
+        R, M = rois.shape[0], int(M)
+        self._loss_dense(rois, torch.float32, (R, 5), "mask_target: rois")
+        self._loss_dense(gt_rows, torch.int32, (R,), "mask_target: gt_rows")
+        if masks.dtype != torch.uint8 or masks.dim() != 3 or (masks.numel() and masks.stride(2) != 1):
+            raise ValueError(f"mask_target: masks must be uint8 [Gtot, H, W] with last stride 1, got {masks.dtype} {tuple(masks.shape)}")
+        Gtot, H, W = masks.shape
+        ldm = max(masks.stride(1), W) if H > 1 else W
+        plane = max(masks.stride(0), H * ldm) if Gtot > 1 else H * ldm
+        if not (1 <= M <= MASK_MAX_MASK and 1 <= H <= MASK_MAX_SIDE and 1 <= W <= MASK_MAX_SIDE and 0 <= R <= MASK_MAX_ROWS):
+            raise ValueError(f"mask_target: limits 1 <= M <= {MASK_MAX_MASK}, 1 <= H, W <= {MASK_MAX_SIDE}, R <= {MASK_MAX_ROWS} "
+                             f"(M = {M}, H = {H}, W = {W}, R = {R})")
+        dt = torch.float32 if soft else torch.uint8
+        if out is None:
+            out = torch.empty(R, M, M, dtype=dt, device=rois.device)
+        self._loss_dense(out, dt, (R, M, M), "mask_target: out")
+        self._ok(self.lib.csm_mask_target(_p(rois), _p(gt_rows), R, _p(masks), Gtot, H, W, ldm, plane, M, int(bool(soft)), _p(out),
+                                          self._stream()), "csm_mask_target")
+        return out
+
+    def mask_loss(self, pred, labels, targets, row_weights, grad=True, out=None, workspace=None):
+        """FCNMaskHead.loss / mask_cross_entropy with its gradient in one call (csm_mask_loss).  pred [R, C, M, M] fp32 contiguous, labels
+        [R] int32 or None (channel 0), targets [R, M, M] uint8 or fp32, row_weights [R] fp32.  -> (out2 = (loss, n) [2], dpred like pred),
+        dpred None with grad=False.  out: the same pair, to own the outputs.  The workspace is cached per device (pass workspace= to own
+        it); calls that share it must share a stream."""
+        self._chk(pred, labels, targets, row_weights)
+        if pred.dim() != 4 or pred.shape[2] != pred.shape[3]:
+            raise ValueError(f"mask_loss: pred must be [R, C, M, M], got {tuple(pred.shape)}")
+        R, C, M, _ = pred.shape
+        f32 = torch.float32
+        self._loss_dense(pred, f32, (R, C, M, M), "mask_loss: pred")
+        if labels is not None:
+            self._loss_dense(labels, torch.int32, (R,), "mask_loss: labels")
+        if targets.dtype not in (torch.uint8, f32):
+            raise ValueError(f"mask_loss: targets must be uint8 or fp32, got {targets.dtype}")
+        self._loss_dense(targets, targets.dtype, (R, M, M), "mask_loss: targets")
+        self._loss_dense(row_weights, f32, (R,), "mask_loss: row_weights")
+        dev = pred.device
+        if out is None:
+            out2, dpred = torch.empty(2, dtype=f32, device=dev), (torch.empty_like(pred) if grad else None)
+        else:
+            out2, dpred = out
+        self._loss_dense(out2, f32, (2,), "mask_loss: out")
+        if dpred is not None:
+            self._loss_dense(dpred, f32, (R, C, M, M), "mask_loss: dpred")
+        need = self.mask_workspace(R)
+        if need <= 0 or R * C * M * M >= 1 << 31:
+            raise ValueError("mask_loss: the shapes are outside the limits of include/clipself_mask.h")
+        ws = self._loss_ws(need, dev, workspace)
+        self._ok(self.lib.csm_mask_loss(_p(pred), _p(labels), _p(targets), int(targets.dtype == f32), _p(row_weights), R, C, M, _p(out2),
+                                        _p(dpred), _p(ws), self._stream()), "csm_mask_loss")
+        return out2, dpred
+
+    def paste_masks(self, logits, labels, boxes, img_h, img_w, thr=0.5, out=None, soft=None):
+        """FCNMaskHead.get_seg_masks / _do_paste_mask (csm_paste_masks).  logits [N, C, M, M] fp32 contiguous, labels [N] int32 or None
+        (channel 0), boxes [N, 4] fp32 contiguous in output-image pixels.  -> out [N, img_h, img_w] uint8 = (v >= thr); soft: an fp32
+        tensor of the same shape that receives v (a test aid).  Nothing is read back."""
+        self._chk(logits, labels, boxes, out, soft)
+        if logits.dim() != 4 or logits.shape[2] != logits.shape[3]:
+            raise ValueError(f"paste_masks: logits must be [N, C, M, M], got {tuple(logits.shape)}")
+        N, C, M, _ = logits.shape
+        img_h, img_w = int(img_h), int(img_w)
+        self._loss_dense(logits, torch.float32, (N, C, M, M), "paste_masks: logits")
+        if labels is not None:
+            self._loss_dense(labels, torch.int32, (N,), "paste_masks: labels")
+        self._loss_dense(boxes, torch.float32, (N, 4), "paste_masks: boxes")
+        if out is None:
+            out = torch.empty(N, img_h, img_w, dtype=torch.uint8, device=logits.device)
+        self._loss_dense(out, torch.uint8, (N, img_h, img_w), "paste_masks: out")
+        if soft is not None:
+            self._loss_dense(soft, torch.float32, (N, img_h, img_w), "paste_masks: soft")
+        self._ok(self.lib.csm_paste_masks(_p(logits), _p(labels), _p(boxes), N, C, M, img_h, img_w, float(thr), _p(out), _p(soft),
+                                          self._stream()), "csm_paste_masks")
+        return out
 
     # -- detector RoI extractor (include/clipself_roi.h) -------------------------------------------------
     def roi_extract_workspace(self, K) -> int:
