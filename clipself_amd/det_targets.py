@@ -593,13 +593,16 @@ def _pos_gt_inds(gt_inds, sel, starts, gt_starts, K, Gtot, Gmax):
 
 
 def rcnn_targets(proposals, gt_bboxes_list, gt_labels_list, assigner, sampler, coder_means=(0., 0., 0., 0.), coder_stds=(.1, .1, .2, .2),
-                 num_classes=65, generator=None, keys=None, ops=None, return_gt_inds=False):
+                 num_classes=65, generator=None, keys=None, ops=None, return_gt_inds=False, proposal_counts=None):
     """StandardRoIHead's assign + sample and BBoxHead.get_targets (reg_class_agnostic=True) for all images, fixed shapes, no read-back on
     the kernel route.  proposals [B, P, 4] or a list of [P_b, 4(+)] tensors.
     -> rois [B * num, 5], labels [B * num] int32, label_weights [B * num], bbox_targets [B * num, 4], bbox_weights [B * num, 4]; slots a
     sampler could not fill are rows with image -1 and zero weights, which SingleRoIExtractor pools to zeros.
     return_gt_inds=True adds a sixth tensor, pos_gt_inds [B * num] int32: the row of the slot's assigned ground truth in the concatenated
-    ground-truth list (what `det_masks.mask_target` indexes the masks with), -1 for negatives and padding slots."""
+    ground-truth list (what `det_masks.mask_target` indexes the masks with), -1 for negatives and padding slots.
+    proposal_counts [B] (a device tensor, as `det_proposals.rpn_proposals` returns it with its fixed-shape proposals): the rows of image b
+    past its count are marked valid = 0 for the assigner -- never matched, never sampled, weights 0 -- so the result equals the list form
+    on the trimmed proposals with the same keys, and nothing is read back."""
     props = [p[:, :4] for p in (proposals if isinstance(proposals, (list, tuple)) else proposals.unbind(0))]
     B, dev = len(props), props[0].device
     if len(gt_bboxes_list) != B or len(gt_labels_list) != B:
@@ -607,16 +610,23 @@ def rcnn_targets(proposals, gt_bboxes_list, gt_labels_list, assigner, sampler, c
     gts, labels, gt_starts, Gmax = _cat_gts(gt_bboxes_list, gt_labels_list, dev)
     Gtot = gts.shape[0]
     prefix = sampler.add_gt_as_proposals
-    parts, starts = [], [0]
+    if proposal_counts is not None and proposal_counts.numel() != B:
+        raise ValueError(f"proposal_counts holds {proposal_counts.numel()} counts for {B} images")
+    parts, starts, live = [], [0], []
     for b in range(B):
         if prefix:
             parts.append(gts[gt_starts[b]:gt_starts[b + 1]])
         parts.append(props[b].to(torch.float32))
         starts.append(starts[-1] + props[b].shape[0] + (gt_starts[b + 1] - gt_starts[b] if prefix else 0))
+        if proposal_counts is not None:                                     # built on the device: the ground-truth prefix rows are valid
+            if prefix:
+                live.append(torch.ones(gt_starts[b + 1] - gt_starts[b], dtype=torch.bool, device=dev))
+            live.append(torch.arange(props[b].shape[0], device=dev) < proposal_counts.reshape(-1)[b].to(dev))
     boxes = torch.cat(parts, dim=0).contiguous()
+    valid = torch.cat(live).to(torch.uint8) if proposal_counts is not None else None
     K, Nmax = boxes.shape[0], max(starts[b + 1] - starts[b] for b in range(B))
     starts_t, gt_starts_t = (_i32(starts, dev), _i32(gt_starts, dev)) if boxes.is_cuda else (starts, gt_starts)
-    gt_inds, _ = assigner.assign_batched(boxes, starts_t, gts, gt_starts_t, B, Nmax, Gmax, prefix, None, ops)
+    gt_inds, _ = assigner.assign_batched(boxes, starts_t, gts, gt_starts_t, B, Nmax, Gmax, prefix, valid, ops)
     if keys is None:
         keys = random_keys((B, Nmax), dev, generator)
     _, sel, _ = sampler.sample_batched(gt_inds, keys, starts_t, K, gt_starts_t, Gtot, Gmax, ops)

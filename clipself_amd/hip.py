@@ -135,6 +135,19 @@ MASK_SIGNATURES = {
 MASK_MAX_ROWS, MASK_MAX_SIDE, MASK_MAX_MASK, MASK_MAX_CLASSES, MASK_MAX_IMAGE = 1 << 20, 2048, 64, 4096, 16384    # include/clipself_mask.h
 
 
+class RpnLevel(ctypes.Structure):
+    """include/clipself_rpn.h: csp_level, one level of the RPN head's maps."""
+    _fields_ = [("cls", _vp), ("reg", _vp), ("h", _i), ("w", _i)]
+
+
+# include/clipself_rpn.h: RPN proposals (per-level top-k, decode, min-size filter).  A seventh header, a seventh table
+RPN_SIGNATURES = {
+    "csp_workspace": (_sz, [ctypes.POINTER(RpnLevel), _i, _i, _i, _i]),
+    "csp_select": (_i, [ctypes.POINTER(RpnLevel), _i, _i, _i, _vp, _l, _i, _f4, _f4, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+RPN_MAX_LEVELS, RPN_MAX_ANCHORS, RPN_MAX_SIDE, RPN_MAX_PRE, RPN_MAX_ROWS = 8, 16, 512, 4096, 16384    # include/clipself_rpn.h
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -164,7 +177,7 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES, MASK_SIGNATURES):
+        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES, MASK_SIGNATURES, RPN_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -205,6 +218,7 @@ class HipOps:
     ASSIGN = True                       # assign / sample / bbox_targets: IoU assignment, random sampling and box-delta targets on the device (det_targets)
     LOSS = True                         # rpn_loss / bbox_head_loss: the RPN's and the box head's losses with their gradients, one call per head (det_losses)
     MASK = True                         # mask_target / mask_loss / paste_masks: the mask branch's targets, loss with gradient and paste (det_masks)
+    RPN = True                          # rpn_select: per-level top-k of the RPN maps, decode and min-size filter, the input of nms' group form (det_proposals)
     BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -1077,6 +1091,85 @@ class HipOps:
                                              _p(bbox_weights), R, C1, int(bg_label), _p(avg_factor), _p(out4), _p(dcls), _p(dbbox), _p(ws),
                                              self._stream()), "csl_bbox_head_loss")
         return out4, dcls, dbbox
+
+    # -- RPN proposals (include/clipself_rpn.h) -----------------------------------------------------------
+    def _rpn_levels(self, cls_scores, bbox_preds, nms_pre):
+        """-> (csp_level array, L, B, A, N, Ktot); ValueError outside the limits of the header."""
+        L = len(cls_scores)
+        if not (1 <= L <= RPN_MAX_LEVELS and len(bbox_preds) == L):
+            raise ValueError(f"rpn_select: {L} cls maps and {len(bbox_preds)} reg maps (1 <= L <= {RPN_MAX_LEVELS})")
+        if cls_scores[0].dim() != 4:
+            raise ValueError(f"rpn_select: level 0: cls must be [B, A, h, w], got {tuple(cls_scores[0].shape)}")
+        B, A = cls_scores[0].shape[0], cls_scores[0].shape[1]
+        nms_pre = int(nms_pre)
+        if not (1 <= B <= 65535 and 1 <= A <= RPN_MAX_ANCHORS and 1 <= nms_pre <= RPN_MAX_PRE):
+            raise ValueError(f"rpn_select: limits 1 <= B <= 65535, 1 <= A <= {RPN_MAX_ANCHORS}, 1 <= nms_pre <= {RPN_MAX_PRE} "
+                             f"(B = {B}, A = {A}, nms_pre = {nms_pre})")
+        arr, N, Ktot = (RpnLevel * L)(), 0, 0
+        for l, (c, r) in enumerate(zip(cls_scores, bbox_preds)):
+            if c.dim() != 4:
+                raise ValueError(f"rpn_select: level {l}: cls must be [B, A, h, w], got {tuple(c.shape)}")
+            h, w = int(c.shape[2]), int(c.shape[3])
+            if not (1 <= h <= RPN_MAX_SIDE and 1 <= w <= RPN_MAX_SIDE):
+                raise ValueError(f"rpn_select: level {l}: h = {h}, w = {w} must be in [1, {RPN_MAX_SIDE}]")
+            self._loss_dense(c, torch.float32, (B, A, h, w), f"rpn_select: level {l}: cls")
+            self._loss_dense(r, torch.float32, (B, 4 * A, h, w), f"rpn_select: level {l}: reg")
+            arr[l] = RpnLevel(c.data_ptr(), r.data_ptr(), h, w)
+            N += h * w * A
+            Ktot += min(nms_pre, h * w * A)
+        if Ktot > RPN_MAX_ROWS:
+            raise ValueError(f"rpn_select: Ktot = {Ktot} rows per image, at most {RPN_MAX_ROWS}")
+        return arr, L, B, A, N, Ktot
+
+    def rpn_select_workspace(self, cls_scores, bbox_preds, nms_pre) -> int:
+        """Bytes of workspace (csp_workspace) for rpn_select on these maps."""
+        arr, L, B, A, _, _ = self._rpn_levels(cls_scores, bbox_preds, nms_pre)
+        return int(self.lib.csp_workspace(arr, L, B, A, int(nms_pre)))
+
+    def rpn_select(self, cls_scores, bbox_preds, anchors, nms_pre, means=(0.0, 0.0, 0.0, 0.0), stds=(1.0, 1.0, 1.0, 1.0), wh_ratio_clip=16 / 1000,
+                   max_shape=None, min_bbox_size=0.0, out=None, workspace=None):
+        """The nms_pre best anchors of every (image, level), decoded and filtered, in one call (csp_select).  cls_scores[l] [B, A, h, w],
+        bbox_preds[l] [B, 4A, h, w] fp32; anchors [N, 4] fp32 with last stride 1 (its row stride is lda), all levels one after another;
+        max_shape [B, 2] = (h, w) fp32 on the device or None.
+        -> (boxes [B * Ktot, 4], scores [B * Ktot], group [B * Ktot] int32, anchor_inds [B * Ktot] int32, starts [B + 1] int32): what nms'
+        group form takes; nothing is read back.  out: the same five, to own the outputs.  The workspace is cached per device (pass
+        workspace= to own it); calls that share it must share a stream."""
+        self._chk(anchors, max_shape, workspace, *cls_scores, *bbox_preds)
+        arr, L, B, A, N, Ktot = self._rpn_levels(cls_scores, bbox_preds, nms_pre)
+        f32, i32, dev = torch.float32, torch.int32, anchors.device
+        if anchors.dtype != f32 or anchors.dim() != 2 or anchors.shape[0] != N or anchors.shape[1] < 4 or anchors.stride(1) != 1:
+            raise ValueError(f"rpn_select: anchors must be fp32 [N = {N}, >= 4] with last stride 1, got {anchors.dtype} {tuple(anchors.shape)}")
+        lda = anchors.stride(0) if N > 1 else max(anchors.stride(0), 4)
+        if lda < 4:
+            raise ValueError(f"rpn_select: the row stride of anchors is {lda}, at least 4 is needed")
+        if max_shape is not None:
+            self._loss_dense(max_shape, f32, (B, 2), "rpn_select: max_shape")
+        if out is None:
+            out = (torch.empty(B * Ktot, 4, dtype=f32, device=dev), torch.empty(B * Ktot, dtype=f32, device=dev),
+                   torch.empty(B * Ktot, dtype=i32, device=dev), torch.empty(B * Ktot, dtype=i32, device=dev),
+                   torch.empty(B + 1, dtype=i32, device=dev))
+        boxes, scores, group, anchor_inds, starts = out
+        self._loss_dense(boxes, f32, (B * Ktot, 4), "rpn_select: boxes")
+        self._loss_dense(scores, f32, (B * Ktot,), "rpn_select: scores")
+        self._loss_dense(group, i32, (B * Ktot,), "rpn_select: group")
+        if anchor_inds is not None:
+            self._loss_dense(anchor_inds, i32, (B * Ktot,), "rpn_select: anchor_inds")
+        self._loss_dense(starts, i32, (B + 1,), "rpn_select: starts")
+        need = int(self.lib.csp_workspace(arr, L, B, A, int(nms_pre)))
+        if need <= 0:
+            raise ValueError("rpn_select: the shapes are outside the limits of include/clipself_rpn.h")
+        if workspace is None:
+            cache = self.__dict__.setdefault("_rpn_ws_cache", {})
+            workspace = cache.get(dev)
+            if workspace is None or workspace.numel() < need:
+                workspace = cache[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+        if workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"rpn_select: workspace holds {workspace.numel() * workspace.element_size()} bytes, {need} are needed")
+        m4, s4 = (_f * 4)(*[float(v) for v in means]), (_f * 4)(*[float(v) for v in stds])
+        self._ok(self.lib.csp_select(arr, L, B, A, _p(anchors), lda, int(nms_pre), m4, s4, float(wh_ratio_clip), _p(max_shape),
+                                     float(min_bbox_size), _p(boxes), _p(scores), _p(group), _p(anchor_inds), _p(starts), _p(workspace),
+                                     self._stream()), "csp_select")
+        return boxes, scores, group, anchor_inds, starts
 
     # -- detector mask branch (include/clipself_mask.h) --------------------------------------------------
     def mask_workspace(self, R) -> int:
