@@ -11,7 +11,7 @@
 //   targets_kernel         one thread per (image, row) or per (image, slot of sel)
 //
 // Every index that comes from device memory (starts, gt_starts, gt_inds, sel) is clamped or compared before it is used.
-#include "cs_common.h"
+#include "det_common.h"
 #include <limits.h>
 #include <math.h>
 
@@ -25,44 +25,22 @@
 
 namespace {
 
-struct Range { int s, n; };
-
-// rows [s, s + n) of image b.  tab is device data: both ends are clamped to [0, total], the length to cap, a non-monotone pair is empty.
-// tab == NULL (boxes only): the shared form, every image owns rows [0, min(total, cap)).
+// img_range of table tab; tab == NULL (boxes only): the shared form, every image owns rows [0, min(total, cap))
 __device__ __forceinline__ Range tab_range(const int* __restrict__ tab, int b, int total, int cap) {
-    Range r;
-    if (tab == nullptr) {
-        r.s = 0;
-        r.n = min(total, cap);
-        return r;
-    }
-    int s = tab[b], e = tab[b + 1];
-    s = min(max(s, 0), total);
-    e = min(max(e, 0), total);
-    r.s = s;
-    r.n = e > s ? min(e - s, cap) : 0;
-    return r;
+    return tab == nullptr ? Range{0, min(total, cap)} : img_range(tab, b, total, cap);
 }
 
-// a rounded product / sum as a value of its own (det_post.hip, `rounded`): no intermediate is ever folded into an fma
-__device__ __forceinline__ float rounded(float p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
-__device__ __forceinline__ float box_area(float x0, float y0, float x1, float y1) {
-    return rounded(__fmul_rn(rounded(__fsub_rn(x1, x0)), rounded(__fsub_rn(y1, y0))));
-}
 // bbox_overlaps, mode 'iou', eps 1e-6, in the header's arithmetic.  The ONE function both passes call, so that iou == gt_max compares the
 // same instructions' results.  Disjoint pairs leave before the division with the 0 the formula gives them (0 / union, union >= 1e-6);
 // a NaN anywhere gives 0: a NaN width fails w > 0, a NaN area makes the union NaN (the comparison keeps it), and NaN != NaN at the end.
 __device__ __forceinline__ float iou_pair(const float4 a, float area_a, const float4 g, float area_g) {
-    const float w = rounded(__fsub_rn(fminf(a.z, g.z), fmaxf(a.x, g.x)));
-    const float h = rounded(__fsub_rn(fminf(a.w, g.w), fmaxf(a.y, g.y)));
+    const float w = f_sub(fminf(a.z, g.z), fmaxf(a.x, g.x));
+    const float h = f_sub(fminf(a.w, g.w), fmaxf(a.y, g.y));
     if (!(w > 0.f && h > 0.f)) return 0.f;
-    const float inter = rounded(__fmul_rn(w, h));
-    const float u = rounded(__fsub_rn(rounded(__fadd_rn(area_a, area_g)), inter));
+    const float inter = f_mul(w, h);
+    const float u = f_sub(f_add(area_a, area_g), inter);
     const float uni = u < 1e-6f ? 1e-6f : u;
-    const float iou = __fdiv_rn(inter, uni);
+    const float iou = f_div(inter, uni);
     return iou == iou ? iou : 0.f;
 }
 
@@ -74,6 +52,13 @@ __device__ __forceinline__ void stage_gts(const float* __restrict__ gt_boxes, lo
         sg[t] = v;
         sa[t] = box_area(v.x, v.y, v.z, v.w);
     }
+}
+
+// Ground truth i's area, read at the top of the iteration next to its corners.  A plain sa[i] is sunk behind iou_pair's early exit, where
+// every intersecting pair then waits for a second LDS round trip (profiles/det_common_ab.md, section 3.1); a volatile read stays put.
+// sa is an LDS array: the pointer names the address space because a volatile generic pointer compiles to a flat system-scope load.
+__device__ __forceinline__ float area_at(const float* sa, int i) {
+    return ((const volatile __attribute__((address_space(3))) float*)sa)[i];
 }
 
 }  // namespace
@@ -129,8 +114,9 @@ __global__ __launch_bounds__(CSA_THREADS) void assign_max_kernel(const float* __
             const float area_a = box_area(a.x, a.y, a.z, a.w);
             float mx = -1.f;
             int arg = 0;
+#pragma unroll 1                                           // one division in flight: unrolled by three is slower with track_gt_max
             for (int i = 0; i < g.n; ++i) {
-                const float v = iou_pair(a, area_a, sg[i], sa[i]);
+                const float v = iou_pair(a, area_a, sg[i], area_at(sa, i));
                 if (v > mx) {
                     mx = v;
                     arg = i;
@@ -186,10 +172,11 @@ __global__ __launch_bounds__(CSA_THREADS) void assign_lowq_kernel(const float* _
     const float4 a = make_float4(p[0], p[1], p[2], p[3]);
     const float area_a = box_area(a.x, a.y, a.z, a.w);
     int hit = -1;
+#pragma unroll 1                                           // as assign_max_kernel
     for (int i = 0; i < g.n; ++i) {
         const float m = sm[i];
         if (m < 0.f) continue;
-        if (iou_pair(a, area_a, sg[i], sa[i]) == m) {
+        if (iou_pair(a, area_a, sg[i], area_at(sa, i)) == m) {
             if (ALL) hit = i;
             else atomicMin(&gt_row[(size_t)b * Gmax + i], row);
         }
@@ -445,28 +432,12 @@ __global__ __launch_bounds__(CSA_SAMPLE_THREADS) void sample_kernel(const int* _
 }
 
 // ------------------------------------------------------------------------------------------------ targets
-struct TgtParams { float mean[4], std[4]; };
-
-// mmdet's bbox2delta then (d - mean) / std, every operation rounded on its own; logf is the only transcendental
-__device__ __forceinline__ void encode_delta(const float* __restrict__ p, const float* __restrict__ q, const TgtParams& prm, float* d) {
-    const float px = rounded(__fmul_rn(rounded(__fadd_rn(p[0], p[2])), 0.5f)), py = rounded(__fmul_rn(rounded(__fadd_rn(p[1], p[3])), 0.5f));
-    const float pw = rounded(__fsub_rn(p[2], p[0])), ph = rounded(__fsub_rn(p[3], p[1]));
-    const float gx = rounded(__fmul_rn(rounded(__fadd_rn(q[0], q[2])), 0.5f)), gy = rounded(__fmul_rn(rounded(__fadd_rn(q[1], q[3])), 0.5f));
-    const float gw = rounded(__fsub_rn(q[2], q[0])), gh = rounded(__fsub_rn(q[3], q[1]));
-    d[0] = __fdiv_rn(rounded(__fsub_rn(gx, px)), pw);
-    d[1] = __fdiv_rn(rounded(__fsub_rn(gy, py)), ph);
-    d[2] = logf(__fdiv_rn(gw, pw));
-    d[3] = logf(__fdiv_rn(gh, ph));
-#pragma unroll
-    for (int c = 0; c < 4; ++c) d[c] = __fdiv_rn(rounded(__fsub_rn(d[c], prm.mean[c])), prm.std[c]);
-}
-
 // grid (ceil(S / 256), B) with S = Nmax (dense, sel == NULL) or num (compact): one thread per output row
 __global__ __launch_bounds__(CSA_THREADS) void targets_kernel(const float* __restrict__ boxes, long ldb, const int* __restrict__ starts, int K,
                                                               const float* __restrict__ gt_boxes, long ldg, const int* __restrict__ gt_labels,
                                                               const int* __restrict__ gt_starts, int Gtot, int Nmax, int Gmax,
                                                               const int* __restrict__ gt_inds, const unsigned char* __restrict__ flags,
-                                                              const int* __restrict__ sel, int num, TgtParams prm, int bg_label,
+                                                              const int* __restrict__ sel, int num, BoxCoder prm, int bg_label,
                                                               float* __restrict__ rois, int* __restrict__ labels,
                                                               float* __restrict__ label_weights, float* __restrict__ bbox_targets,
                                                               float* __restrict__ bbox_weights) {
@@ -495,7 +466,7 @@ __global__ __launch_bounds__(CSA_THREADS) void targets_kernel(const float* __res
     if (pos) {
         if (gt_labels) label = gt_labels[g.s + gi - 1];
         else label = 0;
-        encode_delta(p, gt_boxes + (size_t)(g.s + gi - 1) * ldg, prm, d);
+        encode_delta(prm, p, gt_boxes + (size_t)(g.s + gi - 1) * ldg, d);
     }
     const size_t o = (size_t)b * S + t;
     labels[o] = label;
@@ -600,8 +571,9 @@ extern "C" int csa_targets(const float* boxes, long ldb, const int* starts, int 
     const int S = sel ? num : Nmax;
     if (S == 0) return 0;
     CS_CHECK_ARG(labels && label_weights && bbox_targets && bbox_weights, "csa_targets: the four target outputs must not be NULL");
-    TgtParams prm;
+    BoxCoder prm;                                          // max_ratio belongs to the decode: not read here
     for (int c = 0; c < 4; ++c) prm.mean[c] = means[c], prm.std[c] = stds[c];
+    prm.max_ratio = 0.f;
     hipLaunchKernelGGL(targets_kernel, dim3((S + CSA_THREADS - 1) / CSA_THREADS, B), dim3(CSA_THREADS), 0, stream, boxes, ldb, starts, K, gt_boxes,
                        ldg, gt_labels, gt_starts, Gtot, Nmax, Gmax, gt_inds, flags, sel, num, prm, bg_label, rois, labels, label_weights,
                        bbox_targets, bbox_weights);

@@ -11,12 +11,13 @@
 //   head_finish_kernel     one workgroup: the per-row values in a fixed order -> out[4]
 //
 // Every grid and every order of additions is a function of the host arguments alone.  Labels are compared before they index anything.
-#include "cs_common.h"
+#include "det_common.h"
 #include "../../include/clipself_loss.h"
 #include <float.h>
 #include <limits.h>
-#include <math.h>
 
+// This file predates the rule of det_common.h (f_add / f_sub / f_mul / f_div): its __f*_rn expressions may still contract under this pragma,
+// and stay as they are because un-fusing them would change result bits.  New detector arithmetic takes the f_* of det_common.h.
 #pragma clang fp contract(off)
 
 #define CSL_THREADS 256
@@ -40,14 +41,6 @@ struct RpnArgs {
     int L, B, A;
     long long N;
 };
-
-// the sum of a workgroup's 256 values in a fixed order: butterfly inside each wave, then the four waves in ascending order
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 }  // namespace
 

@@ -13,10 +13,9 @@
 //                          inside the mask are written as 16-byte zero stores; the detection's M * M sigmoids sit in LDS for the rest
 //
 // Every grid is a function of the host arguments alone.  Labels and ground-truth rows are compared before they index anything.
-#include "cs_common.h"
+#include "det_common.h"
 #include "../../include/clipself_mask.h"
 #include <limits.h>
-#include <math.h>
 
 #pragma clang fp contract(off)
 
@@ -28,22 +27,6 @@
 #define CSM_BAND 16                                           // image rows per workgroup of paste_kernel
 
 namespace {
-
-// "Every operation rounded on its own": these four are compiled under the pragma above, so their results carry no permission to contract
-// and the backend cannot fuse a product into a following sum.  (The toolchain's __fmul_rn / __fadd_rn are plain operators in a header that is
-// compiled under the default -ffp-contract=fast: after inlining, a product and a sum of theirs may still become one fma.)
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_sub(float a, float b) { return a - b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_div(float a, float b) { return a / b; }
-
-// the sum of a workgroup's 256 values in a fixed order: butterfly inside each wave, then the four waves in ascending order
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 __device__ __forceinline__ bool finite4(float a, float b, float c, float d) { return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d); }
 

@@ -7,54 +7,20 @@
 //   delta2bbox_kernel one thread per box
 //
 // Every index that comes from device memory (starts, group, the keys in the workspace) is clamped or compared before it is used.
-#include "cs_common.h"
-#include <math.h>
+#include "det_common.h"
 
 #define CSD_MAX_BOXES 16384          // Kmax: 256 bitset words per row = 4 registers per lane of the scanning wave
 #define CSD_MAX_NUM 4096             // the selected keys are sorted in 32 KiB of LDS
 #define CSD_LDS_KEYS 2048            // most keys a scanning wave sorts in LDS (16 KiB); a longer list sorts in the workspace
 #define CSD_TOPK_THREADS 1024
 
-typedef unsigned long long u64;
-
-struct ImgRange { int s, n; };
-
-// rows [s, s + n) of image b: starts is device data, so both ends are clamped to [0, K] and the length to Kmax; a non-monotone pair is empty
-__device__ __forceinline__ ImgRange img_range(const int* __restrict__ starts, int b, int K, int Kmax) {
-    int s = starts[b], e = starts[b + 1];
-    s = min(max(s, 0), K);
-    e = min(max(e, 0), K);
-    ImgRange r;
-    r.s = s;
-    r.n = e > s ? min(e - s, Kmax) : 0;
-    return r;
-}
-
-// float bits -> unsigned with the same order (-0 below +0); NaNs never get here
-__device__ __forceinline__ uint32_t ord_bits(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ord_float(uint32_t o) {
-    return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
-// A rounded product / sum as a value of its own: hipcc's __fmul_rn / __fadd_rn are plain operators in its headers and may be contracted
-// into an fma (roialign_loss.hip, mul_rounded); the empty asm keeps every intermediate of the IoU a rounded fp32 number.
-__device__ __forceinline__ float rounded(float p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
-__device__ __forceinline__ float box_area(float x0, float y0, float x1, float y1) {
-    return rounded(__fmul_rn(rounded(__fsub_rn(x1, x0)), rounded(__fsub_rn(y1, y0))));
-}
 // mmcv nms, offset 0: inter / (area_a + area_b - inter) > thr, fp32, IEEE division.  NaN or 0/0 compares false.
 __device__ __forceinline__ bool iou_gt(const float4 a, float area_a, const float4 b, float area_b, float thr) {
-    const float iw = fmaxf(rounded(__fsub_rn(fminf(a.z, b.z), fmaxf(a.x, b.x))), 0.f);
-    const float ih = fmaxf(rounded(__fsub_rn(fminf(a.w, b.w), fmaxf(a.y, b.y))), 0.f);
-    const float inter = rounded(__fmul_rn(iw, ih));
-    const float uni = rounded(__fsub_rn(rounded(__fadd_rn(area_a, area_b)), inter));
-    return __fdiv_rn(inter, uni) > thr;
+    const float iw = fmaxf(f_sub(fminf(a.z, b.z), fmaxf(a.x, b.x)), 0.f);
+    const float ih = fmaxf(f_sub(fminf(a.w, b.w), fmaxf(a.y, b.y)), 0.f);
+    const float inter = f_mul(iw, ih);
+    const float uni = f_sub(f_add(area_a, area_b), inter);
+    return f_div(inter, uni) > thr;
 }
 
 // ------------------------------------------------------------------------------------------------ mask
@@ -70,7 +36,7 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(const float* __restrict__
     __shared__ int cg[64 * TJ];
     const int tid = threadIdx.x, b = blockIdx.z;
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) img_total[b] = 0;      // the scan kernel's per-image append counter
-    const ImgRange r = img_range(starts, b, K, Kmax);
+    const Range r = img_range(starts, b, K, Kmax);
     if ((int)blockIdx.y * 256 >= r.n) return;
     const int j0 = blockIdx.x * (64 * TJ);
     if (tid < 64 * TJ) {
@@ -110,32 +76,6 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ scan
-// ascending bitonic sort of P (a power of two) keys by nthr threads of one workgroup; keys in LDS or in global memory
-__device__ __forceinline__ void bitonic_sort(u64* keys, int P, int tid, int nthr) {
-    for (int k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += nthr) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int q = i | j;
-                const bool up = (i & k2) == 0;
-                const u64 x = keys[i], y = keys[q];
-                if ((x > y) == up) {
-                    keys[i] = y;
-                    keys[q] = x;
-                }
-            }
-            __threadfence_block();
-            __syncthreads();
-        }
-    }
-}
-
-__device__ __forceinline__ int next_pow2(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 // grid (L, B), 64 threads: one wave owns one list.  L = C (list = class blockIdx.x) or G (list = group blockIdx.x, scores column 0).
 // CAP: keys of LDS per wave, the smallest of 512 / 1024 / 2048 that holds Kmax (more waves per CU for the many short lists of a large C).
 template <int CAP>
@@ -145,7 +85,7 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const float* __restrict__ 
                                                       u64* __restrict__ img_keys, int* __restrict__ img_total, int cap_img) {
     __shared__ u64 lds_keys[CAP];
     const int lane = threadIdx.x, l = blockIdx.x, b = blockIdx.y, L = gridDim.x;
-    const ImgRange r = img_range(starts, b, K, Kmax);
+    const Range r = img_range(starts, b, K, Kmax);
     if (r.n == 0) return;
     // r.n > CAP happens only with CAP = CSD_LDS_KEYS < Kmax, which is when the host passes sort_scratch (Kp keys per list, Kp = pow2 >= Kmax)
     u64* keys = r.n <= CAP ? lds_keys : sort_scratch + ((size_t)b * L + l) * Kp;
@@ -232,7 +172,7 @@ __global__ __launch_bounds__(CSD_TOPK_THREADS) void nms_topk_kernel(const float*
     __shared__ u64 s_prefix;
     __shared__ int s_need, s_cnt;
     const int tid = threadIdx.x, b = blockIdx.x;
-    ImgRange r;
+    Range r;
     r.s = 0;
     r.n = 0;
     int T = 0;
@@ -398,28 +338,14 @@ extern "C" int csd_nms(const float* boxes, long ldb, const float* scores, long l
 }
 
 // ------------------------------------------------------------------------------------------------ delta2bbox
-struct D2BParams { float mean[4], std[4], max_ratio; };
-
-// mmdet 2.x DeltaXYWHBBoxCoder.decode (delta2bbox, add_ctr_clamp=False, clip_border=True), then bboxes / scale_factor.  Every product and
-// sum is rounded on its own (no fma), in the order the reference's tensor expressions evaluate them.
+// mmdet 2.x DeltaXYWHBBoxCoder.decode (decode_box, clip_border=True), then bboxes / scale_factor
 __global__ __launch_bounds__(256) void delta2bbox_kernel(const float* __restrict__ rois, long ldr, const float* __restrict__ deltas, long ldd,
-                                                         const int* __restrict__ starts, int B, int K, D2BParams prm,
+                                                         const int* __restrict__ starts, int B, int K, BoxCoder prm,
                                                          const float* __restrict__ max_shape, const float* __restrict__ scale,
                                                          float* __restrict__ out, long ldo) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= K) return;
-    const float* rp = rois + (size_t)k * ldr;
-    const float* dp = deltas + (size_t)k * ldd;
-    float d[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) d[q] = rounded(__fadd_rn(rounded(__fmul_rn(dp[q], prm.std[q])), prm.mean[q]));
-    const float x0 = rp[0], y0 = rp[1], x1 = rp[2], y1 = rp[3];
-    const float px = rounded(__fmul_rn(rounded(__fadd_rn(x0, x1)), 0.5f)), py = rounded(__fmul_rn(rounded(__fadd_rn(y0, y1)), 0.5f));
-    const float pw = rounded(__fsub_rn(x1, x0)), ph = rounded(__fsub_rn(y1, y0));
-    const float dw = fminf(fmaxf(d[2], -prm.max_ratio), prm.max_ratio), dh = fminf(fmaxf(d[3], -prm.max_ratio), prm.max_ratio);
-    const float gx = rounded(__fadd_rn(px, rounded(__fmul_rn(pw, d[0])))), gy = rounded(__fadd_rn(py, rounded(__fmul_rn(ph, d[1]))));
-    const float hw = rounded(__fmul_rn(rounded(__fmul_rn(pw, expf(dw))), 0.5f)), hh = rounded(__fmul_rn(rounded(__fmul_rn(ph, expf(dh))), 0.5f));
-    float o[4] = {rounded(__fsub_rn(gx, hw)), rounded(__fsub_rn(gy, hh)), rounded(__fadd_rn(gx, hw)), rounded(__fadd_rn(gy, hh))};
+    int b = 0;
     if (max_shape || scale) {
         // image of row k: the number of starts[1..B-1] that are <= k.  starts is device data: the result is an index in [0, B) whatever it holds
         int lo = 0, hi = B - 1;
@@ -427,18 +353,13 @@ __global__ __launch_bounds__(256) void delta2bbox_kernel(const float* __restrict
             const int mid = (lo + hi + 1) >> 1;
             if (starts[mid] <= k) lo = mid; else hi = mid - 1;
         }
-        const int b = lo;
-        if (max_shape) {
-            const float h = max_shape[b * 2], w = max_shape[b * 2 + 1];
-            o[0] = fminf(fmaxf(o[0], 0.f), w);
-            o[1] = fminf(fmaxf(o[1], 0.f), h);
-            o[2] = fminf(fmaxf(o[2], 0.f), w);
-            o[3] = fminf(fmaxf(o[3], 0.f), h);
-        }
-        if (scale) {
+        b = lo;
+    }
+    float o[4];
+    decode_box(prm, rois + (size_t)k * ldr, deltas + (size_t)k * ldd, max_shape ? max_shape + b * 2 : nullptr, o);
+    if (scale) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = __fdiv_rn(o[q], scale[b * 4 + q]);
-        }
+        for (int q = 0; q < 4; ++q) o[q] = f_div(o[q], scale[b * 4 + q]);
     }
     float* op = out + (size_t)k * ldo;
     op[0] = o[0], op[1] = o[1], op[2] = o[2], op[3] = o[3];
@@ -455,9 +376,9 @@ extern "C" int csd_delta2bbox(const float* rois, long ldr, const float* deltas, 
                  "csd_delta2bbox: max_shape / scale are per image and need starts [B + 1] with B >= 1 (B = %d)", B);
     if (K == 0) return 0;
     CS_CHECK_ARG(rois && deltas && out_boxes, "csd_delta2bbox: rois, deltas and out_boxes must not be NULL when K > 0");
-    D2BParams prm;
+    BoxCoder prm;
     for (int q = 0; q < 4; ++q) prm.mean[q] = means[q], prm.std[q] = stds[q];
-    prm.max_ratio = (float)fabs(log((double)wh_ratio_clip));      // np.abs(np.log(wh_ratio_clip)) in double, rounded once where fp32 meets it
+    prm.max_ratio = coder_max_ratio(wh_ratio_clip);
     hipLaunchKernelGGL(delta2bbox_kernel, dim3((K + 255) / 256), dim3(256), 0, stream, rois, ldr, deltas, ldd, starts, B, K, prm, max_shape,
                        scale, out_boxes, ldo);
     CS_LAUNCH_CHECK();

@@ -14,9 +14,8 @@
 //
 // Every grid and trip count is a function of the host arguments alone.  An anchor index that passed through the workspace is compared with
 // the list's length before it indexes anything, and every slot with the list's k before it is written.
-#include "cs_common.h"
+#include "det_common.h"
 #include "../../include/clipself_rpn.h"
-#include <math.h>
 
 #pragma clang fp contract(off)
 
@@ -25,15 +24,7 @@
 #define CSP_BINS 2048                 // bins of one histogram (the third pass uses 1024 of them)
 #define CSP_ROWS_THREADS 1024
 
-typedef unsigned long long u64;
-
 namespace {
-
-// "Every operation rounded on its own": compiled under the pragma above, so no product is fused into a following sum (det_mask.hip).
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_sub(float a, float b) { return a - b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_div(float a, float b) { return a / b; }
 
 struct LevelP {
     const float* cls;
@@ -47,13 +38,10 @@ struct Params {
     LevelP lv[CSP_MAX_LEVELS];
     int L, B, A, Ktot, nms_pre, nlong, chunks;
 };
-struct Decode { float mean[4], std[4], max_ratio, min_size; };
 
-// the sort key of a logit: ~ord(x), smallest = best; NaN = 0xFFFFFFFF, which no number maps to (ord of det_post.hip: -0 below +0)
+// the sort key of a logit: ~ord_bits(x), smallest = best; NaN = 0xFFFFFFFF, which no number maps to
 __device__ __forceinline__ uint32_t key_of(float x) {
-    const uint32_t u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
-    return ~(u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u));
+    return (__float_as_uint(x) & 0x7FFFFFFFu) > 0x7F800000u ? 0xFFFFFFFFu : ~ord_bits(x);
 }
 // logit of anchor i = (y * w + x) * A + a of image b
 __device__ __forceinline__ float logit_at(const LevelP& lv, int A, int b, int i) {
@@ -287,7 +275,7 @@ __global__ __launch_bounds__(CSP_THREADS) void prop_take_kernel(Params p, const 
 
 // ------------------------------------------------------------------------------------------------ sort, decode, store
 // grid (L, B), 1024 threads
-__global__ __launch_bounds__(CSP_ROWS_THREADS) void prop_rows_kernel(Params p, Decode dc, const u64* __restrict__ sel,
+__global__ __launch_bounds__(CSP_ROWS_THREADS) void prop_rows_kernel(Params p, BoxCoder dc, float min_size, const u64* __restrict__ sel,
                                                                      const float* __restrict__ anchors, long lda,
                                                                      const float* __restrict__ max_shape, float* __restrict__ boxes,
                                                                      float* __restrict__ scores, int* __restrict__ group,
@@ -296,8 +284,7 @@ __global__ __launch_bounds__(CSP_ROWS_THREADS) void prop_rows_kernel(Params p, D
     const int tid = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
     const LevelP& lv = p.lv[l];
     const int k = lv.k;                                    // 1 <= k <= nms_pre <= 4096
-    int P2 = 1;
-    while (P2 < k) P2 <<= 1;
+    const int P2 = next_pow2(k);
     if (lv.lng >= 0) {
         const u64* src = sel + (size_t)b * ((size_t)p.nlong * p.nms_pre) + (size_t)lv.lng * p.nms_pre;
         for (int t = tid; t < k; t += CSP_ROWS_THREADS) keys[t] = src[t];
@@ -306,21 +293,7 @@ __global__ __launch_bounds__(CSP_ROWS_THREADS) void prop_rows_kernel(Params p, D
     }
     for (int t = k + tid; t < P2; t += CSP_ROWS_THREADS) keys[t] = ~0ull;
     __syncthreads();
-    for (int k2 = 2; k2 <= P2; k2 <<= 1) {                 // ascending bitonic sort (det_post.hip)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P2 >> 1); t += CSP_ROWS_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int q = i | j;
-                const bool up = (i & k2) == 0;
-                const u64 x = keys[i], y = keys[q];
-                if ((x > y) == up) {
-                    keys[i] = y;
-                    keys[q] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort(keys, P2, tid, CSP_ROWS_THREADS);
     for (int t = tid; t < k; t += CSP_ROWS_THREADS) {
         const size_t row = (size_t)b * p.Ktot + lv.row0 + t;
         const uint32_t i = (uint32_t)keys[t];
@@ -334,24 +307,10 @@ __global__ __launch_bounds__(CSP_ROWS_THREADS) void prop_rows_kernel(Params p, D
             const float* rp = lv.reg + ((size_t)b * 4 * p.A + 4 * a) * lv.hw + pos;
             float d[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) d[q] = f_add(f_mul(rp[(size_t)q * lv.hw], dc.std[q]), dc.mean[q]);
+            for (int q = 0; q < 4; ++q) d[q] = rp[(size_t)q * lv.hw];
             ai = lv.anc0 + (int)i;
-            const float* ap = anchors + (size_t)ai * lda;
-            const float x0 = ap[0], y0 = ap[1], x1 = ap[2], y1 = ap[3];
-            const float px = f_mul(f_add(x0, x1), 0.5f), py = f_mul(f_add(y0, y1), 0.5f);
-            const float pw = f_sub(x1, x0), ph = f_sub(y1, y0);
-            const float dw = fminf(fmaxf(d[2], -dc.max_ratio), dc.max_ratio), dh = fminf(fmaxf(d[3], -dc.max_ratio), dc.max_ratio);
-            const float gx = f_add(px, f_mul(pw, d[0])), gy = f_add(py, f_mul(ph, d[1]));
-            const float hw = f_mul(f_mul(pw, expf(dw)), 0.5f), hh = f_mul(f_mul(ph, expf(dh)), 0.5f);
-            o[0] = f_sub(gx, hw), o[1] = f_sub(gy, hh), o[2] = f_add(gx, hw), o[3] = f_add(gy, hh);
-            if (max_shape) {
-                const float H = max_shape[b * 2], W = max_shape[b * 2 + 1];
-                o[0] = fminf(fmaxf(o[0], 0.f), W);
-                o[1] = fminf(fmaxf(o[1], 0.f), H);
-                o[2] = fminf(fmaxf(o[2], 0.f), W);
-                o[3] = fminf(fmaxf(o[3], 0.f), H);
-            }
-            const bool keep = dc.min_size < 0.f || (f_sub(o[2], o[0]) > dc.min_size && f_sub(o[3], o[1]) > dc.min_size);
+            decode_box(dc, anchors + (size_t)ai * lda, d, max_shape ? max_shape + b * 2 : nullptr, o);
+            const bool keep = min_size < 0.f || (f_sub(o[2], o[0]) > min_size && f_sub(o[3], o[1]) > min_size);
             g = keep ? l : -1;
         }
         float* bp = boxes + row * 4;
@@ -443,10 +402,9 @@ extern "C" int csp_select(const csp_level* levels, int L, int B, int A, const fl
     Params& p = pl.p;
     for (int l = 0; l < L; ++l) p.lv[l].cls = levels[l].cls, p.lv[l].reg = levels[l].reg;
     for (int l = L; l < CSP_MAX_LEVELS; ++l) p.lv[l] = p.lv[0];
-    Decode dc;
+    BoxCoder dc;
     for (int q = 0; q < 4; ++q) dc.mean[q] = means[q], dc.std[q] = stds[q];
-    dc.max_ratio = (float)fabs(log((double)wh_ratio_clip));               // as csd_delta2bbox: in double, rounded once
-    dc.min_size = min_bbox_size;
+    dc.max_ratio = coder_max_ratio(wh_ratio_clip);
     char* ws = (char*)workspace;
     int* hist = (int*)ws;
     int* counts = (int*)(ws + pl.off_counts);
@@ -471,7 +429,7 @@ extern "C" int csp_select(const csp_level* levels, int L, int B, int A, const fl
         hipLaunchKernelGGL(prop_take_kernel, grid, block, 0, stream, p, hist, counts, sel);
         CS_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(prop_rows_kernel, dim3(L, B), dim3(CSP_ROWS_THREADS), 0, stream, p, dc, sel, anchors, lda, max_shape, boxes, scores,
+    hipLaunchKernelGGL(prop_rows_kernel, dim3(L, B), dim3(CSP_ROWS_THREADS), 0, stream, p, dc, min_bbox_size, sel, anchors, lda, max_shape, boxes, scores,
                        group, anchor_inds);
     CS_LAUNCH_CHECK();
     return 0;

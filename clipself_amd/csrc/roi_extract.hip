@@ -11,8 +11,7 @@
 //                            contract's order
 //
 // Every value that comes from device memory (image index, coordinates) is compared before it sizes a loop or forms an index.
-#include "cs_common.h"
-#include <math.h>
+#include "det_common.h"
 
 #define CSR_MAX_LEVELS 4
 #define CSR_MAX_SIDE 512
@@ -43,16 +42,6 @@ struct Levels {
     int L;
 };
 
-// a rounded product / quotient / sum as a value of its own (det_post.hip, `rounded`): hipcc may otherwise contract a * b + c into an fma
-__device__ __forceinline__ float rounded(float p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
-__device__ __forceinline__ float mul_r(float a, float b) { return rounded(__fmul_rn(a, b)); }
-__device__ __forceinline__ float add_r(float a, float b) { return rounded(__fadd_rn(a, b)); }
-__device__ __forceinline__ float sub_r(float a, float b) { return rounded(__fsub_rn(a, b)); }
-__device__ __forceinline__ float div_r(float a, float b) { return rounded(__fdiv_rn(a, b)); }
-
 // What the pooling of one box needs, the same record in the forward and (through the workspace) the backward: 64 bytes.
 struct BoxGeo {
     int b, lvl;                      // b = -1: the box pools to zeros (bounded-box rule, or no samples)
@@ -66,15 +55,15 @@ static_assert(sizeof(BoxGeo) == 64, "the workspace holds 64 bytes per box");
 
 // mmdet 2.x SingleRoIExtractor.map_roi_levels for one box
 __device__ __forceinline__ int roi_level(float x0, float y0, float x1, float y1, float finest_scale, int L) {
-    const float area = mul_r(sub_r(x1, x0), sub_r(y1, y0));
-    const float scale = rounded(__fsqrt_rn(area));
-    const float t = floorf(log2f(add_r(div_r(scale, finest_scale), 1e-6f)));
+    const float area = f_mul(f_sub(x1, x0), f_sub(y1, y0));
+    const float scale = __fsqrt_rn(area);
+    const float t = floorf(log2f(f_add(f_div(scale, finest_scale), 1e-6f)));
     return t >= 1.f ? (int)fminf(t, (float)(L - 1)) : 0;          // NaN compares false: level 0
 }
 
 // sample i of bin p of one axis:  (start + p * bin) + ((i + 0.5) * bin) / grid
 __device__ __forceinline__ float sample_coord(float start, float bin, int grid, int p, int i) {
-    return add_r(add_r(start, mul_r((float)p, bin)), div_r(mul_r((float)i + 0.5f, bin), (float)grid));
+    return f_add(f_add(start, f_mul((float)p, bin)), f_div(f_mul((float)i + 0.5f, bin), (float)grid));
 }
 
 // first and last cell an axis' samples can touch.  The coordinate is monotone in p and in i (every rounded operation is), so its
@@ -96,11 +85,11 @@ __device__ __forceinline__ BoxGeo box_geometry(const float* __restrict__ roi, co
 #pragma unroll
     for (int l = 1; l < CSR_MAX_LEVELS; ++l)
         if (l == g.lvl) s = lv.scale[l], h = lv.h[l], w = lv.w[l];
-    g.sx = sub_r(mul_r(x0, s), 0.5f);
-    g.sy = sub_r(mul_r(y0, s), 0.5f);
-    const float rw = sub_r(sub_r(mul_r(x1, s), 0.5f), g.sx), rh = sub_r(sub_r(mul_r(y1, s), 0.5f), g.sy);
-    g.bw = div_r(rw, (float)P);
-    g.bh = div_r(rh, (float)P);
+    g.sx = f_sub(f_mul(x0, s), 0.5f);
+    g.sy = f_sub(f_mul(y0, s), 0.5f);
+    const float rw = f_sub(f_sub(f_mul(x1, s), 0.5f), g.sx), rh = f_sub(f_sub(f_mul(y1, s), 0.5f), g.sy);
+    g.bw = f_div(rw, (float)P);
+    g.bh = f_div(rh, (float)P);
     // NaN and Inf fail every comparison below that would let the box through
     const bool ok = bf >= 0.f && bf < (float)B && fabsf(rw) <= 2.f * (float)w && fabsf(rh) <= 2.f * (float)h;
     g.gw = g.gh = 0;
@@ -133,8 +122,8 @@ __device__ __forceinline__ bool axis_sample(float c, int size, int& lo, int& hi,
     } else {
         hi = lo + 1;
     }
-    wh = sub_r(c, (float)lo);
-    wl = sub_r(1.f, wh);
+    wh = f_sub(c, (float)lo);
+    wl = f_sub(1.f, wh);
     return true;
 }
 
@@ -196,14 +185,14 @@ __global__ __launch_bounds__(CSR_FWD_THREADS) void roi_extract_fwd_kernel(Levels
                 const size_t o_lo = (size_t)(xc & 0xFFFF) * ld, o_hi = (size_t)(xc >> 16) * ld;
                 const float4 v1 = *(const float4*)(row_lo + o_lo), v2 = *(const float4*)(row_lo + o_hi);
                 const float4 v3 = *(const float4*)(row_hi + o_lo), v4 = *(const float4*)(row_hi + o_hi);
-                fma4(acc, mul_r(hy, hx), v1);
-                fma4(acc, mul_r(hy, lx), v2);
-                fma4(acc, mul_r(ly, hx), v3);
-                fma4(acc, mul_r(ly, lx), v4);
+                fma4(acc, f_mul(hy, hx), v1);
+                fma4(acc, f_mul(hy, lx), v2);
+                fma4(acc, f_mul(ly, hx), v3);
+                fma4(acc, f_mul(ly, lx), v4);
             }
         }
         *(float4*)(out + ((size_t)k * P * P + bin) * ldo + q * 4) =
-            make_float4(__fdiv_rn(acc.x, g.count), __fdiv_rn(acc.y, g.count), __fdiv_rn(acc.z, g.count), __fdiv_rn(acc.w, g.count));
+            make_float4(f_div(acc.x, g.count), f_div(acc.y, g.count), f_div(acc.z, g.count), f_div(acc.w, g.count));
     }
 }
 
@@ -221,16 +210,6 @@ __global__ __launch_bounds__(256) void roi_geom_kernel(Levels lv, int B, const f
 __device__ __forceinline__ bool in_bin(const BoxGeo* __restrict__ geo, int k, int NB, int b0, int l) {
     const int2 id = *(const int2*)&geo[k];
     return id.x >= 0 && id.x % NB == b0 && id.y == l;
-}
-
-__device__ __forceinline__ int block_sum_256(int v, int* part) {       // every thread gets the sum; part: 4 ints of LDS
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) part[tid >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
 }
 
 __global__ __launch_bounds__(256) void roi_bin_count_kernel(const BoxGeo* __restrict__ geo, int K, int NB, int L, int* __restrict__ counts) {
@@ -360,17 +339,17 @@ __global__ __launch_bounds__(64) void roi_extract_bwd_kernel(Levels lv, int C, c
                     int x1 = x0 + 1;
                     while (x1 < nx && (xlist.tag[x1] & 0xFF) == pw) ++x1;
                     float4 gv = *(const float4*)(dk + (size_t)(ph * P + pw) * ldo);
-                    gv = make_float4(__fdiv_rn(gv.x, g.count), __fdiv_rn(gv.y, g.count), __fdiv_rn(gv.z, g.count), __fdiv_rn(gv.w, g.count));
+                    gv = make_float4(f_div(gv.x, g.count), f_div(gv.y, g.count), f_div(gv.z, g.count), f_div(gv.w, g.count));
                     for (int a = y0; a < y1; ++a) {
                         const int ty = ylist.tag[a], rl = (ty >> 8) & 0xFF, rh = (ty >> 16) & 0xFF;
                         const float hy = ylist.wl[a], ly = ylist.wh[a];
                         for (int e = x0; e < x1; ++e) {
                             const int tx = xlist.tag[e], cl = (tx >> 8) & 0xFF, ch = (tx >> 16) & 0xFF;
                             const float hx = xlist.wl[e], lx = xlist.wh[e];
-                            if (rl != 0xFF && cl != 0xFF) { float4 v = acc[rl * CSR_TILE + cl][lane]; fma4(v, mul_r(hy, hx), gv); acc[rl * CSR_TILE + cl][lane] = v; }
-                            if (rl != 0xFF && ch != 0xFF) { float4 v = acc[rl * CSR_TILE + ch][lane]; fma4(v, mul_r(hy, lx), gv); acc[rl * CSR_TILE + ch][lane] = v; }
-                            if (rh != 0xFF && cl != 0xFF) { float4 v = acc[rh * CSR_TILE + cl][lane]; fma4(v, mul_r(ly, hx), gv); acc[rh * CSR_TILE + cl][lane] = v; }
-                            if (rh != 0xFF && ch != 0xFF) { float4 v = acc[rh * CSR_TILE + ch][lane]; fma4(v, mul_r(ly, lx), gv); acc[rh * CSR_TILE + ch][lane] = v; }
+                            if (rl != 0xFF && cl != 0xFF) { float4 v = acc[rl * CSR_TILE + cl][lane]; fma4(v, f_mul(hy, hx), gv); acc[rl * CSR_TILE + cl][lane] = v; }
+                            if (rl != 0xFF && ch != 0xFF) { float4 v = acc[rl * CSR_TILE + ch][lane]; fma4(v, f_mul(hy, lx), gv); acc[rl * CSR_TILE + ch][lane] = v; }
+                            if (rh != 0xFF && cl != 0xFF) { float4 v = acc[rh * CSR_TILE + cl][lane]; fma4(v, f_mul(ly, hx), gv); acc[rh * CSR_TILE + cl][lane] = v; }
+                            if (rh != 0xFF && ch != 0xFF) { float4 v = acc[rh * CSR_TILE + ch][lane]; fma4(v, f_mul(ly, lx), gv); acc[rh * CSR_TILE + ch][lane] = v; }
                         }
                     }
                     x0 = x1;

@@ -23,6 +23,8 @@ import json
 
 import torch
 
+from .det_backend import f32c, kernel_ops
+
 KERNEL_MAX_LEVELS, KERNEL_MAX_ANCHORS, KERNEL_MAX_SIDE = 8, 16, 512      # include/clipself_loss.h
 KERNEL_MAX_ROWS, KERNEL_MAX_CLASSES = 1 << 20, 4096
 FLT_EPSILON = 2.0 ** -23                                                  # mmdet's eps of weight_reduce_loss, torch.finfo(torch.float32).eps
@@ -32,27 +34,9 @@ MASK_BELOW = 1e-5                                                         # Cust
 # against mmdet's formulation in torch on the device, at every shape measured)
 FUSED_LOSS_DEFAULT = True
 
-_hip_ops = None
-
 
 def _kernel_ops(t, ops=None, fused=None):
-    """The backend whose kernels serve tensor t, or None (-> the torch route).  fused=True insists on the kernels."""
-    global _hip_ops
-    if not t.is_cuda:
-        if fused:
-            raise NotImplementedError("fused=True needs CUDA tensors: the kernels have no CPU form")
-        return None
-    if fused is False:
-        return None
-    if ops is None:
-        if _hip_ops is None:
-            from .hip import HipOps
-            _hip_ops = HipOps()
-        ops = _hip_ops
-    has = bool(getattr(ops, "LOSS", False))
-    if fused and not has:
-        raise NotImplementedError(f"fused=True: backend {getattr(ops, 'name', ops)!r} has no LOSS kernels")
-    return ops if has and (fused or FUSED_LOSS_DEFAULT) else None
+    return kernel_ops(t, "LOSS", ops, fused, FUSED_LOSS_DEFAULT)
 
 
 # ================================================================================================ mmdet's loss modules
@@ -270,14 +254,9 @@ class _HeadLossFn(torch.autograd.Function):
 
 
 # ================================================================================================ the batched forms a training loop calls
-def _f32c(t):
-    t = t.float()                                                              # as mmdet's force_fp32
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def _targets(dev, labels, label_weights, bbox_targets, bbox_weights):
-    return (labels.detach().to(device=dev, dtype=torch.int32).contiguous(), _f32c(label_weights.detach().to(dev)),
-            _f32c(bbox_targets.detach().to(dev)), _f32c(bbox_weights.detach().to(dev)))
+    return (labels.detach().to(device=dev, dtype=torch.int32).contiguous(), f32c(label_weights.detach().to(dev)),
+            f32c(bbox_targets.detach().to(dev)), f32c(bbox_weights.detach().to(dev)))
 
 
 def rpn_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, num_total_samples, loss_cls=None, loss_bbox=None,
@@ -312,7 +291,7 @@ def rpn_loss(cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_w
     k_ops = _kernel_ops(cls_scores[0], ops, fused)
     lab, lw, bt, bw = _targets(dev, labels, label_weights, bbox_targets, bbox_weights)
     avg = torch.as_tensor(num_total_samples, device=dev).detach().to(torch.float32).reshape(1)
-    preds = [_f32c(c) for c in cls_scores] + [_f32c(r) for r in bbox_preds]
+    preds = [f32c(c) for c in cls_scores] + [f32c(r) for r in bbox_preds]
     losses = _RpnLossFn.apply(k_ops, L, lab, lw, bt, bw, avg, *preds)
     wc, wb = loss_cls.loss_weight, loss_bbox.loss_weight
     return dict(loss_rpn_cls=[losses[l, 0] * wc if wc != 1.0 else losses[l, 0] for l in range(L)],
@@ -346,6 +325,6 @@ def bbox_head_loss(cls_score, bbox_pred, labels, label_weights, bbox_targets, bb
         raise ValueError(f"bbox_head_loss: class_weight has {cw.numel()} entries for {C1} classes")
     k_ops = _kernel_ops(cls_score, ops, fused)
     lab, lw, bt, bw = _targets(dev, labels, label_weights, bbox_targets, bbox_weights)
-    out4 = _HeadLossFn.apply(k_ops, int(num_classes), lab, lw, bt, bw, cw, None, _f32c(cls_score), _f32c(bbox_pred))
+    out4 = _HeadLossFn.apply(k_ops, int(num_classes), lab, lw, bt, bw, cw, None, f32c(cls_score), f32c(bbox_pred))
     wc, wb = loss_cls.loss_weight, loss_bbox.loss_weight
     return dict(loss_cls=out4[0] * wc if wc != 1.0 else out4[0], acc=out4[1].detach(), loss_bbox=out4[2] * wb if wb != 1.0 else out4[2])

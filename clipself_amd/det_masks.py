@@ -24,6 +24,8 @@ from __future__ import annotations
 
 import torch
 
+from .det_backend import f32c, kernel_ops
+
 KERNEL_MAX_ROWS, KERNEL_MAX_SIDE, KERNEL_MAX_MASK = 1 << 20, 2048, 64        # include/clipself_mask.h
 KERNEL_MAX_CLASSES, KERNEL_MAX_IMAGE = 4096, 16384
 
@@ -33,27 +35,9 @@ FUSED_MASK_DEFAULT = True
 
 _CHUNK = 32                                                                   # rows per step of the torch route
 
-_hip_ops = None
-
 
 def _kernel_ops(t, ops=None, fused=None):
-    """The backend whose kernels serve tensor t, or None (-> the torch route).  fused=True insists on the kernels."""
-    global _hip_ops
-    if not t.is_cuda:
-        if fused:
-            raise NotImplementedError("fused=True needs CUDA tensors: the kernels have no CPU form")
-        return None
-    if fused is False:
-        return None
-    if ops is None:
-        if _hip_ops is None:
-            from .hip import HipOps
-            _hip_ops = HipOps()
-        ops = _hip_ops
-    has = bool(getattr(ops, "MASK", False))
-    if fused and not has:
-        raise NotImplementedError(f"fused=True: backend {getattr(ops, 'name', ops)!r} has no MASK kernels")
-    return ops if has and (fused or FUSED_MASK_DEFAULT) else None
+    return kernel_ops(t, "MASK", ops, fused, FUSED_MASK_DEFAULT)
 
 
 # ================================================================================================ mmdet's loss module
@@ -242,11 +226,6 @@ class _MaskLossFn(torch.autograd.Function):
 
 
 # ================================================================================================ the forms a training / serving loop calls
-def _f32c(t):
-    t = t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def _cat_masks(gt_masks, device):
     if isinstance(gt_masks, torch.Tensor):
         m = gt_masks
@@ -278,7 +257,7 @@ def mask_target(rois, pos_gt_inds, gt_masks, mask_size=28, soft=False, ops=None,
         raise ValueError(f"mask_target: mask_size = {mask_size} must be in [1, {KERNEL_MAX_MASK}]")
     dev = rois.device
     masks = _cat_masks(gt_masks, dev)
-    rois = _f32c(rois.detach())
+    rois = f32c(rois.detach())
     rows = pos_gt_inds.detach().to(device=dev, dtype=torch.int32).contiguous()
     k_ops = _kernel_ops(rois, ops, fused)
     if k_ops is None:
@@ -314,7 +293,7 @@ def mask_loss(mask_pred, mask_targets, labels, row_weights, class_agnostic=True,
         tg = tg.float()
     lab = None if class_agnostic else labels.detach().to(device=dev, dtype=torch.int32).contiguous()
     k_ops = _kernel_ops(mask_pred, ops, fused)
-    out2 = _MaskLossFn.apply(k_ops, lab, tg.contiguous(), _f32c(row_weights.detach().to(dev)), _f32c(mask_pred))
+    out2 = _MaskLossFn.apply(k_ops, lab, tg.contiguous(), f32c(row_weights.detach().to(dev)), f32c(mask_pred))
     w = loss.loss_weight
     return dict(loss_mask=out2[0] * w if w != 1.0 else out2[0])
 
@@ -337,7 +316,7 @@ def paste_masks(mask_pred, det_bboxes, det_labels, img_shape, scale_factor=None,
         boxes = boxes / torch.as_tensor(scale_factor, dtype=torch.float32, device=dev)
     boxes = boxes.contiguous()
     lab = None if class_agnostic else det_labels.detach().to(device=dev, dtype=torch.int32).contiguous()
-    logits = _f32c(mask_pred.detach())
+    logits = f32c(mask_pred.detach())
     k_ops = _kernel_ops(logits, ops, fused)
     if k_ops is None:
         return paste_masks_torch(logits, lab, boxes, img_h, img_w, thr)

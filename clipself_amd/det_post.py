@@ -20,23 +20,14 @@ import math
 
 import torch
 
+from .det_backend import as_i32, kernel_ops
+
 KERNEL_MAX_BOXES = 16384        # include/clipself_det.h: Kmax
 KERNEL_MAX_NUM = 4096           # ... and max_num
 
-_hip_ops = None
-
 
 def _kernel_ops(t, ops=None):
-    """The backend whose kernels serve tensor t, or None (-> the torch route)."""
-    global _hip_ops
-    if not t.is_cuda:
-        return None
-    if ops is None:
-        if _hip_ops is None:
-            from .hip import HipOps
-            _hip_ops = HipOps()
-        ops = _hip_ops
-    return ops if getattr(ops, "DET_POST", False) else None
+    return kernel_ops(t, "DET_POST", ops)
 
 
 def _get(cfg, key, default=None):
@@ -174,12 +165,6 @@ def delta2bbox_torch(rois, deltas, means, stds, wh_ratio_clip, starts=None, max_
 
 
 # ================================================================================================ tensor-level entry points
-def _starts_tensor(starts, device):
-    if isinstance(starts, torch.Tensor):
-        return starts.to(device=device, dtype=torch.int32).contiguous()
-    return torch.tensor([int(v) for v in starts], dtype=torch.int32, device=device)
-
-
 def nms(boxes, scores, starts, Kmax, score_thr, iou_thr, max_num, group=None, G=0, ops=None):
     """Route by tensor: csd_nms on a kernel backend, nms_torch otherwise (and for per-class boxes [K, C, 4])."""
     k_ops = _kernel_ops(boxes, ops) if boxes.dim() == 2 else None
@@ -192,7 +177,7 @@ def nms(boxes, scores, starts, Kmax, score_thr, iou_thr, max_num, group=None, G=
         scores = scores.float().contiguous()
     if group is not None:
         group = group.detach().to(torch.int32).contiguous()
-    return k_ops.nms(boxes, scores, _starts_tensor(starts, boxes.device), Kmax, score_thr, iou_thr, max_num, group, G)
+    return k_ops.nms(boxes, scores, as_i32(starts, boxes.device), Kmax, score_thr, iou_thr, max_num, group, G)
 
 
 def _per_image(v, B, width, device):
@@ -215,7 +200,7 @@ def _decode(rois4, deltas, means, stds, wh_ratio_clip, starts, max_shape, scale,
     if deltas.dtype != torch.float32 or (deltas.shape[0] and deltas.stride(1) != 1):
         deltas = deltas.float().contiguous()
     out = torch.empty(rois4.shape[0], 4, dtype=torch.float32, device=rois4.device)
-    st = None if starts is None else _starts_tensor(starts, rois4.device)
+    st = None if starts is None else as_i32(starts, rois4.device)
     return k_ops.delta2bbox(rois4, deltas, out, means, stds, wh_ratio_clip, st, max_shape, scale)
 
 
@@ -306,7 +291,7 @@ def detections(rois, scores, bbox_pred, img_shapes, scale_factors, score_thr, io
         img_col = rois[:, 0].detach().float().contiguous()
         starts = torch.searchsorted(img_col, torch.arange(B + 1, dtype=torch.float32, device=dev)).to(torch.int32)
     else:
-        starts = _starts_tensor(starts, dev)
+        starts = as_i32(starts, dev)
     ms, sf = _per_image(img_shapes, B, 2, dev), _per_image(scale_factors, B, 4, dev)
     rois4 = rois[:, 1:5]
     if bbox_pred is not None:

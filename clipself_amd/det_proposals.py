@@ -23,6 +23,7 @@ import math
 import torch
 
 from . import det_post
+from .det_backend import f32c, kernel_ops
 
 KERNEL_MAX_LEVELS, KERNEL_MAX_ANCHORS, KERNEL_MAX_SIDE = 8, 16, 512        # include/clipself_rpn.h
 KERNEL_MAX_PRE = 4096           # ... nms_pre
@@ -32,27 +33,9 @@ KERNEL_MAX_ROWS = 16384         # ... Ktot (the Kmax of clipself_det.h)
 # select_torch on the same device, at both shapes measured)
 FUSED_PROPOSALS_DEFAULT = True
 
-_hip_ops = None
-
 
 def _kernel_ops(t, ops=None, fused=None):
-    """The backend whose csp_select serves tensor t, or None (-> select_torch).  fused=True insists on the kernels."""
-    global _hip_ops
-    if fused is False:
-        return None
-    if not t.is_cuda:
-        if fused:
-            raise NotImplementedError("fused=True needs CUDA tensors")
-        return None
-    if ops is None:
-        if _hip_ops is None:
-            from .hip import HipOps
-            _hip_ops = HipOps()
-        ops = _hip_ops
-    has = bool(getattr(ops, "RPN", False))
-    if fused and not has:
-        raise NotImplementedError(f"fused=True: backend {getattr(ops, 'name', ops)!r} has no RPN kernels")
-    return ops if has and (fused or FUSED_PROPOSALS_DEFAULT) else None
+    return kernel_ops(t, "RPN", ops, fused, FUSED_PROPOSALS_DEFAULT)
 
 
 # ================================================================================================ shapes and cfg
@@ -186,13 +169,6 @@ def select_torch(cls_scores, bbox_preds, anchors, max_shape, nms_pre, means=(0.,
 
 
 # ================================================================================================ entry points
-def _f32c(t):
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()                                                              # as mmdet's force_fp32
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def _select(cls_scores, bbox_preds, anchors, img_shapes, nms_pre, means, stds, wh_ratio_clip, min_bbox_size, ops, fused):
     """-> (boxes, scores, levels, anchor_inds as `select` returns them, starts [B + 1] int32 or None on the torch route)."""
     L, B, A, dims, N, Ktot = _layout(cls_scores, bbox_preds, anchors, nms_pre)
@@ -204,8 +180,8 @@ def _select(cls_scores, bbox_preds, anchors, img_shapes, nms_pre, means, stds, w
     anc = anchors.detach().to(device=dev)
     if anc.dtype != torch.float32 or anc.stride(1) != 1:
         anc = anc.float().contiguous()
-    boxes, scores, group, inds, starts = k_ops.rpn_select([_f32c(c) for c in cls_scores], [_f32c(r) for r in bbox_preds], anc, nms_pre, means,
-                                                          stds, wh_ratio_clip, ms, min_bbox_size)
+    boxes, scores, group, inds, starts = k_ops.rpn_select([f32c(c.detach()) for c in cls_scores], [f32c(r.detach()) for r in bbox_preds], anc,
+                                                          nms_pre, means, stds, wh_ratio_clip, ms, min_bbox_size)
     return boxes.view(B, Ktot, 4), scores.view(B, Ktot), group.view(B, Ktot), inds.view(B, Ktot), starts
 
 

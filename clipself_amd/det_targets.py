@@ -25,26 +25,16 @@ import math
 
 import torch
 
+from .det_backend import as_i32, kernel_ops
 from .det_post import delta2bbox  # noqa: F401  (the inverse of bbox2delta; re-exported, not copied)
 
 KERNEL_MAX_ROWS = 1 << 20       # include/clipself_assign.h: Nmax
 KERNEL_MAX_GT = 1024            # ... Gmax
 KERNEL_MAX_NUM = 4096           # ... num
 
-_hip_ops = None
-
 
 def _kernel_ops(t, ops=None):
-    """The backend whose kernels serve tensor t, or None (-> the torch route)."""
-    global _hip_ops
-    if not t.is_cuda:
-        return None
-    if ops is None:
-        if _hip_ops is None:
-            from .hip import HipOps
-            _hip_ops = HipOps()
-        ops = _hip_ops
-    return ops if getattr(ops, "ASSIGN", False) else None
+    return kernel_ops(t, "ASSIGN", ops)
 
 
 # ================================================================================================ anchors
@@ -354,14 +344,6 @@ def _f32_rows(t):
     return t
 
 
-def _i32(t, device):
-    if t is None:
-        return None
-    if isinstance(t, torch.Tensor):
-        return t.to(device=device, dtype=torch.int32).contiguous()
-    return torch.tensor([int(v) for v in t], dtype=torch.int32, device=device)
-
-
 def _check_limits(Nmax, Gmax, num=1):
     if not (0 <= Nmax <= KERNEL_MAX_ROWS and 0 <= Gmax <= KERNEL_MAX_GT and 1 <= num <= KERNEL_MAX_NUM):
         raise ValueError(f"the kernel route takes at most {KERNEL_MAX_ROWS} boxes and {KERNEL_MAX_GT} ground truths per image and "
@@ -378,7 +360,7 @@ def assign(boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax, pos_iou_thr, neg_i
     _check_limits(Nmax, Gmax)
     dev = boxes.device
     valid = None if valid is None else valid.detach().to(device=dev, dtype=torch.uint8).contiguous()
-    return k_ops.assign(_f32_rows(boxes), _i32(starts, dev), _f32_rows(gt_boxes.to(dev)), _i32(gt_starts, dev), B, Nmax, Gmax, pos_iou_thr,
+    return k_ops.assign(_f32_rows(boxes), as_i32(starts, dev), _f32_rows(gt_boxes.to(dev)), as_i32(gt_starts, dev), B, Nmax, Gmax, pos_iou_thr,
                         neg_iou_thr, min_pos_iou, match_low_quality, gt_max_assign_all, gt_prefix, valid)
 
 
@@ -391,7 +373,7 @@ def sample(gt_inds, keys, starts, K, gt_starts, Gtot, Gmax, num, expected_pos, n
     dev = gt_inds.device
     if keys.dtype == torch.int64:
         keys = keys.to(torch.int32)                                         # wraps: the low 32 bits
-    return k_ops.sample(gt_inds.contiguous(), keys.to(dev).contiguous(), _i32(starts, dev), K, _i32(gt_starts, dev), Gtot, Gmax, num,
+    return k_ops.sample(gt_inds.contiguous(), keys.to(dev).contiguous(), as_i32(starts, dev), K, as_i32(gt_starts, dev), Gtot, Gmax, num,
                         expected_pos, neg_pos_ub)
 
 
@@ -403,7 +385,7 @@ def bbox_targets(boxes, starts, gt_boxes, gt_labels, gt_starts, Gmax, gt_inds, f
         return targets_torch(boxes, starts, gt_boxes, gt_labels, gt_starts, Gmax, gt_inds, flags, sel, means, stds, bg_label, pos_weight)
     _check_limits(gt_inds.shape[1], Gmax, 1 if sel is None else sel.shape[1])
     dev = boxes.device
-    return k_ops.bbox_targets(_f32_rows(boxes), _i32(starts, dev), _f32_rows(gt_boxes.to(dev)), _i32(gt_labels, dev), _i32(gt_starts, dev), Gmax,
+    return k_ops.bbox_targets(_f32_rows(boxes), as_i32(starts, dev), _f32_rows(gt_boxes.to(dev)), as_i32(gt_labels, dev), as_i32(gt_starts, dev), Gmax,
                               gt_inds.contiguous(), None if flags is None else flags.contiguous(), None if sel is None else sel.contiguous(),
                               means, stds, bg_label, pos_weight)
 
@@ -565,7 +547,7 @@ def rpn_targets(anchors, valid, gt_bboxes_list, assigner, sampler, coder_means=(
     Gtot = gts.shape[0]
     anchors = _f32_rows(anchors)
     valid = None if valid is None else valid.to(torch.uint8)
-    gt_starts_t = _i32(gt_starts, dev) if anchors.is_cuda else gt_starts
+    gt_starts_t = as_i32(gt_starts, dev) if anchors.is_cuda else gt_starts
     gt_inds, _ = assigner.assign_batched(anchors, None, gts, gt_starts_t, B, N, Gmax, False, valid, ops)
     if keys is None:
         keys = random_keys((B, N), dev, generator)
@@ -625,7 +607,7 @@ def rcnn_targets(proposals, gt_bboxes_list, gt_labels_list, assigner, sampler, c
     boxes = torch.cat(parts, dim=0).contiguous()
     valid = torch.cat(live).to(torch.uint8) if proposal_counts is not None else None
     K, Nmax = boxes.shape[0], max(starts[b + 1] - starts[b] for b in range(B))
-    starts_t, gt_starts_t = (_i32(starts, dev), _i32(gt_starts, dev)) if boxes.is_cuda else (starts, gt_starts)
+    starts_t, gt_starts_t = (as_i32(starts, dev), as_i32(gt_starts, dev)) if boxes.is_cuda else (starts, gt_starts)
     gt_inds, _ = assigner.assign_batched(boxes, starts_t, gts, gt_starts_t, B, Nmax, Gmax, prefix, valid, ops)
     if keys is None:
         keys = random_keys((B, Nmax), dev, generator)

@@ -19,24 +19,15 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from .det_backend import kernel_ops
+
 KERNEL_MAX_LEVELS = 4           # include/clipself_roi.h
 KERNEL_MAX_OUTPUT = 14
 KERNEL_MAX_SAMPLING = 8
 
-_hip_ops = None
-
 
 def _kernel_ops(t, ops=None):
-    """The backend whose kernels serve tensor t, or None (-> the torch route)."""
-    global _hip_ops
-    if not t.is_cuda:
-        return None
-    if ops is None:
-        if _hip_ops is None:
-            from .hip import HipOps
-            _hip_ops = HipOps()
-        ops = _hip_ops
-    return ops if getattr(ops, "ROI_EXTRACT", False) else None
+    return kernel_ops(t, "ROI_EXTRACT", ops)
 
 
 def bbox2roi(bbox_list):

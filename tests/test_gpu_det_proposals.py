@@ -7,7 +7,8 @@ n = nms_pre (a list no longer than nms_pre skips the select: pre{1,7,64,2000}_n*
 per list in the select passes: n2048_pre64 / n2050_pre64 -- 2049 = 3 * 683 is no h * w * A inside the limits) and k = 2048 (one or two
 rounds of the 1024 sorting threads: pre2000_n2001 / n2050_pre2049).  1999 is a prime above 512, so 1998 stands in for nms_pre - 1 at
 nms_pre = 2000.  Known answers bit for bit; end to end through HipOps and through det_proposals.rpn_proposals with call counters; the chain
-into rcnn_targets(proposal_counts=) without a read-back; read / write extents inside the poisoned halos of tests/_extents.py."""
+into rcnn_targets(proposal_counts=) without a read-back; read / write extents inside the poisoned halos of tests/_extents.py.  The two
+callers of det_common.h's decode_box (csp_select, csd_delta2bbox) are held to equal bits on clamped and clipped rows."""
 import numpy as np
 import pytest
 import torch
@@ -104,6 +105,58 @@ def test_known_answers_bit_for_bit(hip):
     assert _run(hip, sat)[3].tolist() == [[5, 4, 3]]                                    # by logit, though every score is 1
     no_clamp = dict(_known_case(-1.0), max_shape=None)
     assert np.array_equal(_bits(_run(hip, no_clamp)[0][0]), _bits(c["anchors"]))
+
+
+# ------------------------------------------------------------------------------------------------ the two callers of decode_box
+DECODE_SEED = 0          # chosen on the CPU with select_torch / delta2bbox_torch: both lists of both nms_pre hold clamped and clipped rows
+
+
+def _decode_case():
+    """Two levels (4 x 4 and 2 x 3), A = 3, B = 2; unscaled randn deltas against wh_ratio_clip = 0.5 (the clamp is at |d| = ln 2, so about
+    half of dw / dh hit it); anchors that reach past the small max_shape; min_bbox_size = -1 keeps every row."""
+    g = torch.Generator().manual_seed(DECODE_SEED)
+    dims, A, B = [(4, 4), (2, 3)], 3, 2
+    cls = [torch.randn(B, A, h, w, generator=g) for h, w in dims]
+    reg = [torch.randn(B, 4 * A, h, w, generator=g) for h, w in dims]
+    N = sum(h * w * A for h, w in dims)
+    ctr, half = torch.rand(N, 2, generator=g) * 64.0, torch.rand(N, 2, generator=g) * 20.0 + 2.0
+    anchors = torch.cat([ctr - half, ctr + half], dim=1)
+    return dict(cls=cls, reg=reg, anchors=anchors, max_shape=torch.tensor([[40.0, 48.0], [36.0, 44.0]]), means=(0.05, -0.1, 0.2, -0.15),
+                stds=(0.5, 0.6, 1.1, 0.9), wh_ratio_clip=0.5, A=A)
+
+
+def _gather_deltas(reg, inds, A):
+    """The four raw deltas of anchor inds[b, t] (index into the concatenated anchor list) from the [B, 4A, h, w] maps -> [B, Ktot, 4]."""
+    flat = torch.cat([r.reshape(r.shape[0], A, 4, -1).permute(0, 3, 1, 2).reshape(r.shape[0], -1, 4) for r in reg], dim=1)     # [B, N, 4]
+    return torch.gather(flat, 1, inds.long().unsqueeze(-1).expand(-1, -1, 4))
+
+
+@pytest.mark.parametrize("nms_pre", [64, 8])          # every list short (no select) / every list long (the select path)
+def test_select_and_delta2bbox_decode_to_the_same_bits(hip, nms_pre):
+    """prop_rows_kernel and delta2bbox_kernel both call decode_box of det_common.h: every row of csp_select equals csd_delta2bbox of that
+    row's anchor and its four deltas, bit for bit -- and some of the rows are clamped at max_ratio, some clipped at max_shape."""
+    c = _decode_case()
+    cls, reg = [x.cuda() for x in c["cls"]], [x.cuda() for x in c["reg"]]
+    anchors, ms = c["anchors"].cuda(), c["max_shape"].cuda()
+    boxes, _, _, inds, starts = hip.rpn_select(cls, reg, anchors, nms_pre, c["means"], c["stds"], c["wh_ratio_clip"], ms, -1.0)
+    B = ms.shape[0]
+    Ktot = boxes.shape[0] // B
+    assert Ktot == sum(min(nms_pre, x[0].numel()) for x in c["cls"])
+    rows = inds >= 0
+    assert bool(rows.all())                                                                # no anchor index is out of range
+    rois = anchors[inds.long()]
+    deltas = _gather_deltas(reg, inds.view(B, Ktot), c["A"]).reshape(B * Ktot, 4).contiguous()
+    want = hip.delta2bbox(rois, deltas, torch.empty_like(boxes), c["means"], c["stds"], c["wh_ratio_clip"], starts, ms, None)
+    free = hip.delta2bbox(rois, deltas, torch.empty_like(boxes), c["means"], c["stds"], c["wh_ratio_clip"])
+    torch.cuda.synchronize()
+    bad = torch.nonzero((boxes != want).any(dim=1) & rows)[:, 0].tolist()
+    assert torch.equal(boxes[rows], want[rows]), f"rows {bad[:8]}: select {boxes[bad[:8]].tolist()} delta2bbox {want[bad[:8]].tolist()}"
+    f = lambda v: torch.tensor(v, device="cuda")
+    d = deltas * f(c["stds"]) + f(c["means"])
+    clamped = (d[:, 2:].abs() > abs(np.log(c["wh_ratio_clip"])) + 1e-3).any(dim=1)
+    clipped = (free != want).any(dim=1)
+    print(f"nms_pre {nms_pre}: {B * Ktot} rows, {int(clamped.sum())} clamped, {int(clipped.sum())} clipped")
+    assert int(clamped.sum()) >= 1 and int(clipped.sum()) >= 1 and int((~clamped).sum()) >= 1 and int((~clipped).sum()) >= 1
 
 
 # ------------------------------------------------------------------------------------------------ end to end
