@@ -148,6 +148,14 @@ RPN_SIGNATURES = {
 RPN_MAX_LEVELS, RPN_MAX_ANCHORS, RPN_MAX_SIDE, RPN_MAX_PRE, RPN_MAX_ROWS = 8, 16, 512, 4096, 16384    # include/clipself_rpn.h
 
 
+# include/clipself_conv.h: the detector heads' 3 x 3 convolutions (implicit GEMM, explicit matrix).  An eighth header, an eighth table
+CONV_SIGNATURES = {
+    "csc_conv3x3": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
+    "csc_im2col3x3": (_i, [_vp, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _vp]),
+}
+CONV_MAX_ROWS = (1 << 31) - 512                          # include/clipself_conv.h: N * H * W
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -177,7 +185,8 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES, MASK_SIGNATURES, RPN_SIGNATURES):
+        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES, MASK_SIGNATURES, RPN_SIGNATURES,
+                      CONV_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -219,6 +228,7 @@ class HipOps:
     LOSS = True                         # rpn_loss / bbox_head_loss: the RPN's and the box head's losses with their gradients, one call per head (det_losses)
     MASK = True                         # mask_target / mask_loss / paste_masks: the mask branch's targets, loss with gradient and paste (det_masks)
     RPN = True                          # rpn_select: per-level top-k of the RPN maps, decode and min-size filter, the input of nms' group form (det_proposals)
+    CONV3X3 = True                      # conv3x3 / im2col3x3: Conv2d(Cin, Cout, 3, padding=1) on channel-last rows as an implicit GEMM (conv.Conv3x3)
     BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -1170,6 +1180,69 @@ class HipOps:
                                      float(min_bbox_size), _p(boxes), _p(scores), _p(group), _p(anchor_inds), _p(starts), _p(workspace),
                                      self._stream()), "csp_select")
         return boxes, scores, group, anchor_inds, starts
+
+    # -- 3 x 3 convolutions of the detector heads (include/clipself_conv.h) ---------------------------------
+    @staticmethod
+    def _conv_map(t, N, H, W, who):
+        """A map as the header states it: bf16 rows [N*H*W, C], last stride 1, a row stride that is a multiple of 8, 16-byte aligned."""
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[0] != N * H * W or t.stride(1) != 1:
+            raise ValueError(f"{who} must be bf16 rows [N*H*W = {N * H * W}, C] with last stride 1, got {t.dtype} {tuple(t.shape)} {t.stride()}")
+        ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+        if ld < t.shape[1] or ld % 8 or t.data_ptr() % 16:
+            raise ValueError(f"{who}: row stride {ld} must be a multiple of 8 that holds {t.shape[1]} channels, the base 16-byte aligned")
+        return ld
+
+    def conv3x3(self, x, Wg, y, bias, N, H, W):
+        """y[p, co] = bias[co] + sum_{t, ci} x[p shifted by tap t, ci] * Wg[co, t*Cin + ci] (csc_conv3x3): Conv2d(Cin, Cout, 3, padding=1)
+        on channel-last rows.  x bf16 [N*H*W, Cin] (row stride % 8 == 0), Wg bf16 [Cout, 9*Cin], bias fp32 [Cout] or None, y fp32 or bf16
+        [N*H*W, Cout] (row stride % 4 == 0).  Cin % 64 == 0 and Cout % 8 == 0, else ValueError."""
+        self._chk(x, Wg, y, bias)
+        N, H, W = int(N), int(H), int(W)
+        if min(N, H, W) < 1 or N * H * W > CONV_MAX_ROWS:
+            raise ValueError(f"conv3x3: 1 <= N*H*W <= {CONV_MAX_ROWS} (N = {N}, H = {H}, W = {W})")
+        ldx = self._conv_map(x, N, H, W, "conv3x3: x")
+        Cin = x.shape[1]
+        if Wg.dtype != torch.bfloat16 or Wg.dim() != 2 or Wg.shape[1] != 9 * Cin or Wg.stride(1) != 1 or Wg.stride(0) % 8 or Wg.data_ptr() % 16:
+            raise ValueError(f"conv3x3: Wg must be bf16 [Cout, 9*Cin = {9 * Cin}] with 16-byte aligned rows, got {Wg.dtype} {tuple(Wg.shape)}")
+        Cout = Wg.shape[0]
+        if Cin % 64 or Cout % 8:
+            raise ValueError(f"conv3x3: outside the kernel's coverage (Cin % 64 == 0, Cout % 8 == 0): Cin = {Cin}, Cout = {Cout}")
+        if y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 2 or tuple(y.shape) != (N * H * W, Cout) or y.stride(1) != 1:
+            raise ValueError(f"conv3x3: y must be fp32 / bf16 rows [{N * H * W}, {Cout}] with last stride 1, got {y.dtype} {tuple(y.shape)}")
+        ldy = y.stride(0) if y.shape[0] > 1 else max(y.stride(0), Cout)
+        if ldy < Cout or ldy % 4 or y.data_ptr() % 16:
+            raise ValueError(f"conv3x3: y's row stride {ldy} must be a multiple of 4 that holds {Cout} channels, the base 16-byte aligned")
+        if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,) or not bias.is_contiguous() or bias.data_ptr() % 16):
+            raise ValueError(f"conv3x3: bias must be contiguous fp32 [{Cout}], 16-byte aligned")
+        rc = self.lib.csc_conv3x3(_p(x), ldx, _p(Wg), max(Wg.stride(0), 9 * Cin), _p(bias), _p(y), ldy, _dt(y), N, H, W, Cin, Cout, self._stream())
+        if rc == 1:
+            raise ValueError("csc_conv3x3: shape outside the kernel's coverage")
+        self._ok(rc, "csc_conv3x3")
+
+    def im2col3x3(self, x, cols, N, H, W, row0=0):
+        """cols[r, t*Cin + ci] = x[(row0 + r) shifted by tap t, ci], zero where the tap leaves the image (csc_im2col3x3): rows
+        [row0, row0 + cols.shape[0]) of the explicit matrix.  x bf16 [N*H*W, Cin], cols bf16 [rows, 9*Cin] (row strides % 8 == 0; columns
+        past 9*Cin of a wider row are left alone).  Cin % 8 == 0, else ValueError."""
+        self._chk(x, cols)
+        N, H, W, row0 = int(N), int(H), int(W), int(row0)
+        if min(N, H, W) < 1 or N * H * W > CONV_MAX_ROWS:
+            raise ValueError(f"im2col3x3: 1 <= N*H*W <= {CONV_MAX_ROWS} (N = {N}, H = {H}, W = {W})")
+        ldx = self._conv_map(x, N, H, W, "im2col3x3: x")
+        Cin = x.shape[1]
+        if Cin % 8:
+            raise ValueError(f"im2col3x3: outside the kernel's coverage (Cin % 8 == 0): Cin = {Cin}")
+        if cols.dtype != torch.bfloat16 or cols.dim() != 2 or cols.shape[1] != 9 * Cin or cols.stride(1) != 1:
+            raise ValueError(f"im2col3x3: cols must be bf16 [rows, 9*Cin = {9 * Cin}] with last stride 1, got {cols.dtype} {tuple(cols.shape)}")
+        rows = cols.shape[0]
+        ldc = cols.stride(0) if rows > 1 else max(cols.stride(0), 9 * Cin)
+        if ldc < 9 * Cin or ldc % 8 or cols.data_ptr() % 16:
+            raise ValueError(f"im2col3x3: cols' row stride {ldc} must be a multiple of 8 that holds {9 * Cin} columns, the base 16-byte aligned")
+        if not (0 <= row0 and row0 + rows <= N * H * W):
+            raise ValueError(f"im2col3x3: rows [{row0}, {row0 + rows}) outside the map's {N * H * W} rows")
+        rc = self.lib.csc_im2col3x3(_p(x), ldx, _p(cols), ldc, row0, rows, N, H, W, Cin, self._stream())
+        if rc == 1:
+            raise ValueError("csc_im2col3x3: shape outside the kernel's coverage")
+        self._ok(rc, "csc_im2col3x3")
 
     # -- detector mask branch (include/clipself_mask.h) --------------------------------------------------
     def mask_workspace(self, R) -> int:
