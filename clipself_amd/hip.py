@@ -156,6 +156,19 @@ CONV_SIGNATURES = {
 CONV_MAX_ROWS = (1 << 31) - 512                          # include/clipself_conv.h: N * H * W
 
 
+# include/clipself_bn.h: batch norm (+ ReLU) on channel-last maps, forward and backward.  A ninth header, a ninth table
+BN_SIGNATURES = {
+    "csb_row_parts": (_i, [_l, _i]),
+    "csb_workspace": (_sz, [_l, _i]),
+    "csb_stats": (_i, [_vp, _l, _i, _l, _i, _vp, _vp, _vp]),
+    "csb_finalize": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
+    "csb_apply": (_i, [_vp, _l, _i, _vp, _i, _vp, _l, _i, _l, _i, _vp]),
+    "csb_bwd_reduce": (_i, [_vp, _l, _i, _vp, _l, _i, _vp, _i, _vp, _vp, _l, _i, _vp]),
+    "csb_bwd_apply": (_i, [_vp, _l, _i, _vp, _l, _i, _vp, _i, _vp, _vp, _vp, _l, _i, _l, _i, _vp]),
+}
+BN_MAX_ROWS, BN_MAX_C, BN_MAX_RECORDS, BN_REC_EXTRA, BN_ST_EXTRA = (1 << 31) - 512, 65536, 4096, 4, 4      # include/clipself_bn.h
+
+
 class AttnExtra(ctypes.Structure):
     """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
     _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
@@ -186,7 +199,7 @@ def load_library():
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
         for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES, MASK_SIGNATURES, RPN_SIGNATURES,
-                      CONV_SIGNATURES):
+                      CONV_SIGNATURES, BN_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -229,6 +242,7 @@ class HipOps:
     MASK = True                         # mask_target / mask_loss / paste_masks: the mask branch's targets, loss with gradient and paste (det_masks)
     RPN = True                          # rpn_select: per-level top-k of the RPN maps, decode and min-size filter, the input of nms' group form (det_proposals)
     CONV3X3 = True                      # conv3x3 / im2col3x3: Conv2d(Cin, Cout, 3, padding=1) on channel-last rows as an implicit GEMM (conv.Conv3x3)
+    BATCHNORM = True                    # bn_stats / bn_finalize / bn_apply / bn_bwd_reduce / bn_bwd_apply: batch norm (+ ReLU) on channel-last rows (norm_act.BatchNormAct2d)
     BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -1243,6 +1257,140 @@ class HipOps:
         if rc == 1:
             raise ValueError("csc_im2col3x3: shape outside the kernel's coverage")
         self._ok(rc, "csc_im2col3x3")
+
+    # -- batch norm (+ ReLU) on channel-last maps (include/clipself_bn.h) --------------------------------
+    @staticmethod
+    def _bn_map(t, M, C, who):
+        """A map as the header states it: fp32 / bf16 rows [M, C], last stride 1, row stride % 4 (fp32) or % 8 (bf16), 16-byte aligned."""
+        if t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 2 or tuple(t.shape) != (M, C) or t.stride(1) != 1:
+            raise ValueError(f"{who} must be fp32 / bf16 rows [{M}, {C}] with last stride 1, got {t.dtype} {tuple(t.shape)} {t.stride()}")
+        ld = t.stride(0) if M > 1 else max(t.stride(0), C)
+        if ld < C or ld % (8 if t.dtype == torch.bfloat16 else 4) or t.data_ptr() % 16:
+            raise ValueError(f"{who}: row stride {ld} must be a multiple of 8 (bf16) / 4 (fp32) that holds {C} channels, the base 16-byte aligned")
+        return ld
+
+    @staticmethod
+    def _bn_shape(x, who):
+        if x.dim() != 2:
+            raise ValueError(f"{who}: a map is 2-D rows [M, C], got {tuple(x.shape)}")
+        M, C = x.shape
+        if not (1 <= M <= BN_MAX_ROWS and 1 <= C <= BN_MAX_C):
+            raise ValueError(f"{who}: 1 <= M <= {BN_MAX_ROWS}, 1 <= C <= {BN_MAX_C} (M = {M}, C = {C})")
+        if C % 8:
+            raise ValueError(f"{who}: outside the kernels' coverage (C % 8 == 0): C = {C}")
+        return M, C
+
+    @staticmethod
+    def _bn_vec(t, n, who, optional=False):
+        if t is None and optional:
+            return
+        if t is None or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"{who} must be contiguous fp32 with {n} elements, 16-byte aligned")
+
+    @staticmethod
+    def _bn_stream(t):
+        """The current stream of t's device as a raw handle.  These wrappers run five times per layer and step, where
+        torch.cuda.current_stream() (a Python object per call) is a tenth of the host time; the raw getter is what torch's own
+        compiled code paths use."""
+        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+        return raw(t.device.index) if raw is not None else torch.cuda.current_stream(t.device).cuda_stream
+
+    def _bn_rc(self, rc, who):
+        if rc == 1:
+            raise ValueError(f"{who}: shape outside the kernels' coverage")
+        self._ok(rc, who)
+
+    def bn_workspace(self, M, C) -> int:
+        """Bytes of per-part partial sums (csb_workspace) that bn_stats and bn_bwd_reduce need for a map of M rows and C channels."""
+        sizes = self.__dict__.setdefault("_bn_ws_sizes", {})
+        need = sizes.get((M, C))
+        if need is None:
+            need = sizes[(M, C)] = int(self.lib.csb_workspace(int(M), int(C)))
+        return need
+
+    def _bn_ws(self, ws, M, C, who, dev):
+        need = self.bn_workspace(M, C)
+        if ws is None:
+            cache = self.__dict__.setdefault("_bn_ws_cache", {})
+            ws = cache.get(dev)
+            if ws is None or ws.numel() < need:
+                ws = cache[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+        if ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+            raise ValueError(f"{who}: workspace holds {ws.numel() * ws.element_size()} bytes, {need} (16-byte aligned) are needed")
+        return ws
+
+    def bn_stats(self, x, rec, ws=None):
+        """This rank's record of the map x [M, C] (csb_stats): rec fp32 [2*C + 4] = mean | M2 = sum (x - mean)^2 | the row count as int32 bits."""
+        self._chk(x, rec, ws)
+        M, C = self._bn_shape(x, "bn_stats")
+        ldx = self._bn_map(x, M, C, "bn_stats: x")
+        self._bn_vec(rec, 2 * C + BN_REC_EXTRA, "bn_stats: rec")
+        ws = self._bn_ws(ws, M, C, "bn_stats", x.device)
+        self._bn_rc(self.lib.csb_stats(_p(x), ldx, _dt(x), M, C, _p(rec), _p(ws), self._bn_stream(x)), "csb_stats")
+
+    def bn_finalize(self, recs, C, gamma, beta, eps, momentum, running_mean, running_var, st):
+        """The state st fp32 [4*C + 4] = mean | rstd | scale | shift | 1/N (csb_finalize) from recs fp32 [R, 2*C + 4] merged in ascending order
+        by count (training; running_mean / running_var updated in place where given) or, with recs=None, from the running statistics."""
+        self._chk(recs, gamma, beta, running_mean, running_var, st)
+        C = int(C)
+        if not 1 <= C <= BN_MAX_C:
+            raise ValueError(f"bn_finalize: 1 <= C <= {BN_MAX_C} (C = {C})")
+        if C % 8:
+            raise ValueError(f"bn_finalize: outside the kernels' coverage (C % 8 == 0): C = {C}")
+        R = 0
+        if recs is not None:
+            if recs.dim() == 1:
+                recs = recs.view(1, -1)
+            R = recs.shape[0]
+            if not 1 <= R <= BN_MAX_RECORDS:
+                raise ValueError(f"bn_finalize: 1 <= R <= {BN_MAX_RECORDS} records (R = {R})")
+            self._bn_vec(recs, R * (2 * C + BN_REC_EXTRA), "bn_finalize: recs")
+        elif running_mean is None or running_var is None:
+            raise ValueError("bn_finalize: recs=None (evaluation mode) needs running_mean and running_var")
+        if not float(eps) >= 0.0:
+            raise ValueError(f"bn_finalize: eps >= 0 (eps = {eps})")
+        for t, who in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+            self._bn_vec(t, C, f"bn_finalize: {who}", optional=True)
+        self._bn_vec(st, 4 * C + BN_ST_EXTRA, "bn_finalize: st")
+        self._bn_rc(self.lib.csb_finalize(_p(recs), R, C, _p(gamma), _p(beta), float(eps), float(momentum), _p(running_mean), _p(running_var),
+                                          _p(st), self._bn_stream(st)), "csb_finalize")
+
+    @staticmethod
+    def _bn_act(act):
+        if act not in (0, 1):
+            raise ValueError(f"act is 0 (none) or 1 (ReLU), got {act!r}")
+        return int(act)
+
+    def bn_apply(self, x, st, act, y):
+        """y = act(fmaf(x, scale[c], shift[c])) (csb_apply): x, y fp32 / bf16 [M, C], st from bn_finalize, act 0 = none, 1 = ReLU."""
+        self._chk(x, st, y)
+        M, C = self._bn_shape(x, "bn_apply")
+        ldx, ldy = self._bn_map(x, M, C, "bn_apply: x"), self._bn_map(y, M, C, "bn_apply: y")
+        self._bn_vec(st, 4 * C + BN_ST_EXTRA, "bn_apply: st")
+        self._bn_rc(self.lib.csb_apply(_p(x), ldx, _dt(x), _p(st), self._bn_act(act), _p(y), ldy, _dt(y), M, C, self._bn_stream(x)), "csb_apply")
+
+    def bn_bwd_reduce(self, dy, x, st, act, sums, ws=None):
+        """sums fp32 [2*C] = sum g | sum g * xhat over the rows (csb_bwd_reduce), g = dy under the ReLU mask recomputed from x and st."""
+        self._chk(dy, x, st, sums, ws)
+        M, C = self._bn_shape(x, "bn_bwd_reduce")
+        lddy, ldx = self._bn_map(dy, M, C, "bn_bwd_reduce: dy"), self._bn_map(x, M, C, "bn_bwd_reduce: x")
+        self._bn_vec(st, 4 * C + BN_ST_EXTRA, "bn_bwd_reduce: st")
+        self._bn_vec(sums, 2 * C, "bn_bwd_reduce: sums")
+        ws = self._bn_ws(ws, M, C, "bn_bwd_reduce", x.device)
+        self._bn_rc(self.lib.csb_bwd_reduce(_p(dy), lddy, _dt(dy), _p(x), ldx, _dt(x), _p(st), self._bn_act(act), _p(sums), _p(ws), M, C,
+                                            self._bn_stream(x)), "csb_bwd_reduce")
+
+    def bn_bwd_apply(self, dy, x, st, act, sums, gamma, dx):
+        """dx = gamma * rstd * (g - sum g / N - xhat * sum g xhat / N) (csb_bwd_apply); without the last two terms when st is an
+        evaluation-mode state.  gamma fp32 [C] or None."""
+        self._chk(dy, x, st, sums, gamma, dx)
+        M, C = self._bn_shape(x, "bn_bwd_apply")
+        lddy, ldx, lddx = (self._bn_map(t, M, C, f"bn_bwd_apply: {n}") for t, n in ((dy, "dy"), (x, "x"), (dx, "dx")))
+        self._bn_vec(st, 4 * C + BN_ST_EXTRA, "bn_bwd_apply: st")
+        self._bn_vec(sums, 2 * C, "bn_bwd_apply: sums")
+        self._bn_vec(gamma, C, "bn_bwd_apply: gamma", optional=True)
+        self._bn_rc(self.lib.csb_bwd_apply(_p(dy), lddy, _dt(dy), _p(x), ldx, _dt(x), _p(st), self._bn_act(act), _p(sums), _p(gamma), _p(dx), lddx,
+                                           _dt(dx), M, C, self._bn_stream(x)), "csb_bwd_apply")
 
     # -- detector mask branch (include/clipself_mask.h) --------------------------------------------------
     def mask_workspace(self, R) -> int:
