@@ -8,6 +8,7 @@
 // MFMA GEMMs read.  A flag byte per 64 elements carries (bit0) "has a gradient this step" and (bit1)
 // "weight decay applies".  The kernel is a pure HBM stream: 4 fp32 reads + 3 fp32 writes + 1 bf16 write per element.
 #include "cs_common.h"
+#include "../../include/clipself_hip.h"
 
 namespace {
 
@@ -57,13 +58,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, const float* hea
 }
 
 // ---- gradient norm of the guarded step: partial sums of squares (a) and their combination (b), no atomics, fixed summation order.
-// Mirrors of CS_ADAMW_GUARD_HEAD / CS_ADAMW_GUARD_SPAN in include/clipself_hip.h (tests/test_adamw_guard_cpu.py holds them together).
-constexpr int GUARD_HEAD = 8;
-constexpr int GUARD_SPAN = 16384;
-constexpr int GUARD_CHUNKS = GUARD_SPAN / 256;         // 256-element chunks per partial: 64, 16 per wave
+// The buffer's layout is the header's: CS_ADAMW_GUARD_HEAD floats, then one partial per CS_ADAMW_GUARD_SPAN elements.
+constexpr int GUARD_CHUNKS = CS_ADAMW_GUARD_SPAN / 256;        // 256-element chunks per partial: 64, 16 per wave
 constexpr int GUARD_FINAL_THREADS = 256;
 
-// (a) workgroup k -> guard[GUARD_HEAD + k] = sum over the active granules of [k * SPAN, (k + 1) * SPAN) of (grad_scale * g)^2, whatever the
+// (a) workgroup k -> guard[CS_ADAMW_GUARD_HEAD + k] = sum over the active granules of [k * SPAN, (k + 1) * SPAN) of (grad_scale * g)^2, whatever the
 // grid: wave w takes chunks w, w + 4, ... of the span with adamw_kernel's chunk / flag-byte addressing; inactive granules and chunks past n are not loaded.
 // Rounding depth of one element's path: scale (counts twice under the square), square, 16 adds in a lane component, 2 to fold the 4
 // components, 6 shuffle levels, 2 across the 4 waves -- at most 29 fp32 roundings; the rest of the sum is done in double by (b), which
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(256) void guard_partial_kernel(const float* __restr
 __global__ __launch_bounds__(GUARD_FINAL_THREADS) void guard_finalize_kernel(float* guard, long npartials, float max_norm, int skip_nonfinite) {
     __shared__ double tsum[GUARD_FINAL_THREADS];
     double s = 0.0;
-    for (long k = threadIdx.x; k < npartials; k += GUARD_FINAL_THREADS) s += (double)guard[GUARD_HEAD + k];
+    for (long k = threadIdx.x; k < npartials; k += GUARD_FINAL_THREADS) s += (double)guard[CS_ADAMW_GUARD_HEAD + k];
     tsum[threadIdx.x] = s;
     __syncthreads();
     for (int off = GUARD_FINAL_THREADS / 2; off > 0; off >>= 1) {
@@ -148,8 +147,8 @@ extern "C" int cs_adamw_step(float* p, const float* g, float* m, float* v, void*
         CS_LAUNCH_CHECK();
         return 0;
     }
-    const long npartials = (n + GUARD_SPAN - 1) / GUARD_SPAN;
-    hipLaunchKernelGGL(guard_partial_kernel, dim3((int)npartials), dim3(256), 0, stream, g, flags, a.nchunks, grad_scale, guard + GUARD_HEAD);
+    const long npartials = (n + CS_ADAMW_GUARD_SPAN - 1) / CS_ADAMW_GUARD_SPAN;
+    hipLaunchKernelGGL(guard_partial_kernel, dim3((int)npartials), dim3(256), 0, stream, g, flags, a.nchunks, grad_scale, guard + CS_ADAMW_GUARD_HEAD);
     CS_LAUNCH_CHECK();
     hipLaunchKernelGGL(guard_finalize_kernel, dim3(1), dim3(GUARD_FINAL_THREADS), 0, stream, guard, npartials, max_norm, skip_nonfinite);
     CS_LAUNCH_CHECK();

@@ -17,6 +17,7 @@
 //     14x14(+CLS) grid a single chunk of 224 covers all 197 keys and no rescale is ever taken.
 #include <type_traits>
 #include "cs_common.h"
+#include "../../include/clipself_hip.h"
 #include <cstdlib>
 
 namespace {
@@ -1592,17 +1593,6 @@ extern "C" size_t cs_attn_bwd_workspace(int B, int Ntok, int H, int Q) {
     if (Q <= 0) return img;
     return ((img + 255) & ~(size_t)255) + (size_t)B * H * ((Ntok + PKB - 1) / PKB) * Q * HD * sizeof(float);
 }
-
-// C-side mirror of include/clipself_hip.h's cs_attn_extra
-struct cs_attn_extra {
-    const void* q;
-    const void* o;
-    const void* dout;
-    const float* lse;
-    const unsigned char* allow;
-    void* dq;
-    int Q, ldq, ldo, lddq;
-};
 
 static int attn_bwd_image(const void* qkv, const void* o, const void* dout, const float* lse, const float* cos_t, const float* sin_t,
                           void* dqkv, void* workspace, int B, int Ntok, int H, int ldqkv, int ldo, float scale, hipStream_t stream) {

@@ -12,7 +12,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define CS_WAVE 64
 
 // ---- error plumbing (no exceptions across the C ABI) -------------------------------------
-extern "C" const char* cs_last_error();
 void cs_set_error(const char* fmt, ...);
 #define CS_CHECK_ARG(cond, ...)            \
     do {                                   \

@@ -12,14 +12,12 @@
 //
 // Every index that comes from device memory (starts, gt_starts, gt_inds, sel) is clamped or compared before it is used.
 #include "det_common.h"
+#include "../../include/clipself_assign.h"
 #include <limits.h>
 #include <math.h>
 
 #pragma clang fp contract(off)
 
-#define CSA_MAX_ROWS (1 << 20)
-#define CSA_MAX_GT 1024
-#define CSA_MAX_NUM 4096
 #define CSA_THREADS 256
 #define CSA_SAMPLE_THREADS 1024
 

@@ -8,9 +8,10 @@
 //
 // Every index that comes from device memory (starts, group, the keys in the workspace) is clamped or compared before it is used.
 #include "det_common.h"
+#include "../../include/clipself_det.h"
 
-#define CSD_MAX_BOXES 16384          // Kmax: 256 bitset words per row = 4 registers per lane of the scanning wave
-#define CSD_MAX_NUM 4096             // the selected keys are sorted in 32 KiB of LDS
+// CSD_MAX_BOXES (Kmax): 256 bitset words per row = 4 registers per lane of the scanning wave; CSD_MAX_NUM: the selected keys are
+// sorted in 32 KiB of LDS
 #define CSD_LDS_KEYS 2048            // most keys a scanning wave sorts in LDS (16 KiB); a longer list sorts in the workspace
 #define CSD_TOPK_THREADS 1024
 

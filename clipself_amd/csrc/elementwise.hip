@@ -1,6 +1,7 @@
 // HBM-bound helper kernels of the CLIPSelf step: SiLU*mul (fwd/bwd), f32->bf16 cast, padded bf16 transpose,
 // column sums (bias gradients), patch im2row, CLS-row fill.  All vectorised to 16-byte accesses per lane.
 #include "cs_common.h"
+#include "../../include/clipself_hip.h"
 
 namespace {
 

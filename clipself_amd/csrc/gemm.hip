@@ -29,6 +29,7 @@
 //   * workgroup ids are remapped so that each XCD owns a contiguous range of tiles, rasterised in groups of 8 M panels
 //     (B tiles stay in that XCD's 4 MiB L2 while 8 A panels stream past).
 #include "gemm_common.h"
+#include "../../include/clipself_hip.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace {

@@ -39,6 +39,7 @@
 #include <vector>
 #include <cstdio>
 #include "gemm_common.h"
+#include "../../include/clipself_hip.h"
 
 namespace {
 

@@ -6,6 +6,7 @@
 //   ffn_ln, final norm: eva_vit_model.py:306-307,218,102,616) and F.normalize(dim=-1, eps=1e-12)
 //   (eva_vit_model.py:620).
 #include "cs_common.h"
+#include "../../include/clipself_hip.h"
 
 namespace {
 

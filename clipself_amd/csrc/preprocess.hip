@@ -10,6 +10,7 @@
 // One call handles the K boxes of ONE decoded image (HWC uint8, resident in HBM): pass 1 writes the horizontally resampled rows of
 // every crop to a workspace, pass 2 resamples vertically, pads and normalises into out[K,3,S,S] fp32.
 #include "cs_common.h"
+#include "../../include/clipself_hip.h"
 
 // Pillow is compiled for baseline x86-64 (no FMA): keep every multiply and add separately rounded, as its C code executes them.
 #pragma clang fp contract(off)

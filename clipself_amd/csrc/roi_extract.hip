@@ -12,24 +12,14 @@
 //
 // Every value that comes from device memory (image index, coordinates) is compared before it sizes a loop or forms an index.
 #include "det_common.h"
+#include "../../include/clipself_roi.h"
 
-#define CSR_MAX_LEVELS 4
-#define CSR_MAX_SIDE 512
-#define CSR_MAX_P 14
-#define CSR_MAX_SR 8
 #define CSR_TAB 1040                 // samples of one axis of one box: P * grid <= |extent| + P <= 2 * 512 + 14 (sampling_ratio: <= 14 * 8)
 #define CSR_FWD_THREADS 256
 #define CSR_TILE 4                   // backward: cells per tile side
 #define CSR_BWD_QUADS 64             // backward: float4 channel groups per workgroup (one wave)
 #define CSR_LIST 128                 // backward: samples of one axis of one box that touch one tile (bound derived at build_list)
 #define CSR_MAX_BINS 4096            // backward: (image % 1024, level) bins the boxes are sorted into
-
-struct csr_level {                   // == include/clipself_roi.h
-    float* map;
-    long ld;
-    int h, w;
-    float spatial_scale;
-};
 
 namespace {
 

@@ -11,6 +11,7 @@
 // per-row / per-column weights Wy[h], Wx[w] (sequentially, fixed order -> deterministic) and then touches each
 // map cell at most once:   pooled = sum_{r,c} Wy[r] Wx[c] F[r,c] / max(gh*gw,1).
 #include "cs_common.h"
+#include "../../include/clipself_hip.h"
 
 namespace {
 

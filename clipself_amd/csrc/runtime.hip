@@ -9,6 +9,7 @@
 #include <cstdint>
 #include "cs_common.h"
 #include "gemm_common.h"
+#include "../../include/clipself_hip.h"
 
 extern "C" int cs_num_compute_units(void) { return cs_num_cus(); }
 

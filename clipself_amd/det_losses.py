@@ -24,9 +24,8 @@ import json
 import torch
 
 from .det_backend import f32c, kernel_ops
-
-KERNEL_MAX_LEVELS, KERNEL_MAX_ANCHORS, KERNEL_MAX_SIDE = 8, 16, 512      # include/clipself_loss.h
-KERNEL_MAX_ROWS, KERNEL_MAX_CLASSES = 1 << 20, 4096
+from .hip import (LOSS_MAX_ANCHORS as KERNEL_MAX_ANCHORS, LOSS_MAX_CLASSES as KERNEL_MAX_CLASSES, LOSS_MAX_LEVELS as KERNEL_MAX_LEVELS,  # include/clipself_loss.h
+                  LOSS_MAX_ROWS as KERNEL_MAX_ROWS, LOSS_MAX_SIDE as KERNEL_MAX_SIDE)
 FLT_EPSILON = 2.0 ** -23                                                  # mmdet's eps of weight_reduce_loss, torch.finfo(torch.float32).eps
 MASK_BELOW = 1e-5                                                         # CustomCrossEntropyLoss: class_weight < 1e-5 masks the class
 

@@ -25,9 +25,8 @@ from __future__ import annotations
 import torch
 
 from .det_backend import f32c, kernel_ops
-
-KERNEL_MAX_ROWS, KERNEL_MAX_SIDE, KERNEL_MAX_MASK = 1 << 20, 2048, 64        # include/clipself_mask.h
-KERNEL_MAX_CLASSES, KERNEL_MAX_IMAGE = 4096, 16384
+from .hip import (MASK_MAX_CLASSES as KERNEL_MAX_CLASSES, MASK_MAX_IMAGE as KERNEL_MAX_IMAGE, MASK_MAX_MASK as KERNEL_MAX_MASK,  # include/clipself_mask.h
+                  MASK_MAX_ROWS as KERNEL_MAX_ROWS, MASK_MAX_SIDE as KERNEL_MAX_SIDE)
 
 # fused=None takes the kernels where the backend has them (tools/det_masks_bench.py, profiles/det_masks_bench.md: against the torch route of
 # this module on the same device, at every shape measured)

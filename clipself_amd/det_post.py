@@ -21,9 +21,7 @@ import math
 import torch
 
 from .det_backend import as_i32, kernel_ops
-
-KERNEL_MAX_BOXES = 16384        # include/clipself_det.h: Kmax
-KERNEL_MAX_NUM = 4096           # ... and max_num
+from .hip import DET_MAX_BOXES as KERNEL_MAX_BOXES, DET_MAX_NUM as KERNEL_MAX_NUM      # include/clipself_det.h: Kmax and max_num
 
 
 def _kernel_ops(t, ops=None):

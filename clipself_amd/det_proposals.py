@@ -24,10 +24,9 @@ import torch
 
 from . import det_post
 from .det_backend import f32c, kernel_ops
-
-KERNEL_MAX_LEVELS, KERNEL_MAX_ANCHORS, KERNEL_MAX_SIDE = 8, 16, 512        # include/clipself_rpn.h
-KERNEL_MAX_PRE = 4096           # ... nms_pre
-KERNEL_MAX_ROWS = 16384         # ... Ktot (the Kmax of clipself_det.h)
+# include/clipself_rpn.h: PRE bounds nms_pre, ROWS bounds Ktot (the Kmax of clipself_det.h)
+from .hip import (RPN_MAX_ANCHORS as KERNEL_MAX_ANCHORS, RPN_MAX_LEVELS as KERNEL_MAX_LEVELS, RPN_MAX_PRE as KERNEL_MAX_PRE,
+                  RPN_MAX_ROWS as KERNEL_MAX_ROWS, RPN_MAX_SIDE as KERNEL_MAX_SIDE)
 
 # fused=None takes csp_select where the backend has it (tools/det_proposals_bench.py, profiles/det_proposals_bench.md: against
 # select_torch on the same device, at both shapes measured)

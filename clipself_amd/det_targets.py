@@ -27,10 +27,7 @@ import torch
 
 from .det_backend import as_i32, kernel_ops
 from .det_post import delta2bbox  # noqa: F401  (the inverse of bbox2delta; re-exported, not copied)
-
-KERNEL_MAX_ROWS = 1 << 20       # include/clipself_assign.h: Nmax
-KERNEL_MAX_GT = 1024            # ... Gmax
-KERNEL_MAX_NUM = 4096           # ... num
+from .hip import ASSIGN_MAX_GT as KERNEL_MAX_GT, ASSIGN_MAX_NUM as KERNEL_MAX_NUM, ASSIGN_MAX_ROWS as KERNEL_MAX_ROWS  # include/clipself_assign.h: Gmax, num, Nmax
 
 
 def _kernel_ops(t, ops=None):

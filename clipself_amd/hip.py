@@ -19,11 +19,13 @@ _LIB_PATH = Path(os.environ["CLIPSELF_HIP_LIB"]) if os.environ.get("CLIPSELF_HIP
 
 EPI_BF16, EPI_F32, EPI_RESID_F32, EPI_SWIGLU_BF16, EPI_ATOMIC_F32, EPI_PATCH_F32, EPI_RESID_LN_F32, EPI_GELU_BF16, EPI_QGELU_BF16 = range(9)
 DX_BF16, DX_F32_ASSIGN, DX_F32_ACCUM = range(3)
-ADAMW_GUARD_HEAD, ADAMW_GUARD_SPAN = 8, 16384          # CS_ADAMW_GUARD_HEAD / CS_ADAMW_GUARD_SPAN of the header
+ADAMW_GUARD_HEAD, ADAMW_GUARD_SPAN = 8, 16384
 
 _vp, _i, _l, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_size_t
+_F32, _F32_BF16 = (torch.float32,), (torch.float32, torch.bfloat16)
 
-# name -> (restype, argtypes); must list every symbol declared in include/clipself_hip.h
+# name -> (restype, argtypes), one table per public header; the Python constant beside a table restates a macro of that header (MACROS)
+# include/clipself_hip.h: the engines
 SIGNATURES = {
     "cs_last_error": (ctypes.c_char_p, []),
     "cs_gemm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -79,12 +81,18 @@ SIGNATURES = {
 }
 
 
-# include/clipself_det.h: detector post-processing.  Not an engine op, so not part of SIGNATURES (which mirrors clipself_hip.h one to one)
+class AttnExtra(ctypes.Structure):
+    """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
+    _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
+
+
+# include/clipself_det.h: detector post-processing
 DET_SIGNATURES = {
     "csd_nms_workspace": (_sz, [_i, _i, _i, _i]),
     "csd_nms": (_i, [_vp, _l, _vp, _l, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "csd_delta2bbox": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _f, _vp, _vp, _vp, _l, _vp]),
 }
+DET_MAX_BOXES, DET_MAX_NUM = 16384, 4096                 # Kmax, max_num
 
 
 class RoiLevel(ctypes.Structure):
@@ -92,15 +100,16 @@ class RoiLevel(ctypes.Structure):
     _fields_ = [("map", _vp), ("ld", _l), ("h", _i), ("w", _i), ("spatial_scale", _f)]
 
 
-# include/clipself_roi.h: the detector's multi-level RoIAlign, forward and backward.  A third header, a third table
+# include/clipself_roi.h: the detector's multi-level RoIAlign, forward and backward
 ROI_SIGNATURES = {
     "csr_roi_extract_workspace": (_sz, [_i]),
     "csr_roi_extract_fwd": (_i, [ctypes.POINTER(RoiLevel), _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _l, _vp]),
     "csr_roi_extract_bwd": (_i, [_vp, _l, _vp, _i, _i, _i, _f, ctypes.POINTER(RoiLevel), _i, _i, _i, _vp, _vp]),
 }
+ROI_MAX_LEVELS, ROI_MAX_SIDE, ROI_MAX_P, ROI_MAX_SR = 4, 512, 14, 8
 
 
-# include/clipself_assign.h: the detector's training targets (IoU assignment, sampling, box deltas).  A fourth header, a fourth table
+# include/clipself_assign.h: the detector's training targets (IoU assignment, sampling, box deltas)
 _f4 = ctypes.POINTER(_f)
 ASSIGN_SIGNATURES = {
     "csa_workspace": (_sz, [_i, _i, _i, _i]),
@@ -108,7 +117,7 @@ ASSIGN_SIGNATURES = {
     "csa_sample": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "csa_targets": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f4, _f4, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
-ASSIGN_MAX_ROWS, ASSIGN_MAX_GT, ASSIGN_MAX_NUM = 1 << 20, 1024, 4096       # include/clipself_assign.h: Nmax, Gmax, num
+ASSIGN_MAX_ROWS, ASSIGN_MAX_GT, ASSIGN_MAX_NUM = 1 << 20, 1024, 4096       # Nmax, Gmax, num
 
 
 class LossLevel(ctypes.Structure):
@@ -116,23 +125,23 @@ class LossLevel(ctypes.Structure):
     _fields_ = [("cls", _vp), ("reg", _vp), ("dcls", _vp), ("dreg", _vp), ("h", _i), ("w", _i)]
 
 
-# include/clipself_loss.h: the detector's losses with their gradients (RPN and box head).  A fifth header, a fifth table
+# include/clipself_loss.h: the detector's losses with their gradients (RPN and box head)
 LOSS_SIGNATURES = {
     "csl_workspace": (_sz, [ctypes.POINTER(LossLevel), _i, _i, _i, _i]),
     "csl_rpn_loss": (_i, [ctypes.POINTER(LossLevel), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "csl_bbox_head_loss": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
-LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_SIDE, LOSS_MAX_ROWS, LOSS_MAX_CLASSES = 8, 16, 512, 1 << 20, 4096    # include/clipself_loss.h
+LOSS_MAX_LEVELS, LOSS_MAX_ANCHORS, LOSS_MAX_SIDE, LOSS_MAX_ROWS, LOSS_MAX_CLASSES = 8, 16, 512, 1 << 20, 4096
 
 
-# include/clipself_mask.h: the detector's mask branch (mask targets, mask loss with gradient, mask paste).  A sixth header, a sixth table
+# include/clipself_mask.h: the detector's mask branch (mask targets, mask loss with gradient, mask paste)
 MASK_SIGNATURES = {
     "csm_workspace": (_sz, [_i]),
     "csm_mask_target": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _l, _l, _i, _i, _vp, _vp]),
     "csm_mask_loss": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "csm_paste_masks": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
 }
-MASK_MAX_ROWS, MASK_MAX_SIDE, MASK_MAX_MASK, MASK_MAX_CLASSES, MASK_MAX_IMAGE = 1 << 20, 2048, 64, 4096, 16384    # include/clipself_mask.h
+MASK_MAX_ROWS, MASK_MAX_GT, MASK_MAX_SIDE, MASK_MAX_MASK, MASK_MAX_CLASSES, MASK_MAX_IMAGE = 1 << 20, 1 << 24, 2048, 64, 4096, 16384
 
 
 class RpnLevel(ctypes.Structure):
@@ -140,23 +149,23 @@ class RpnLevel(ctypes.Structure):
     _fields_ = [("cls", _vp), ("reg", _vp), ("h", _i), ("w", _i)]
 
 
-# include/clipself_rpn.h: RPN proposals (per-level top-k, decode, min-size filter).  A seventh header, a seventh table
+# include/clipself_rpn.h: RPN proposals (per-level top-k, decode, min-size filter)
 RPN_SIGNATURES = {
     "csp_workspace": (_sz, [ctypes.POINTER(RpnLevel), _i, _i, _i, _i]),
     "csp_select": (_i, [ctypes.POINTER(RpnLevel), _i, _i, _i, _vp, _l, _i, _f4, _f4, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
-RPN_MAX_LEVELS, RPN_MAX_ANCHORS, RPN_MAX_SIDE, RPN_MAX_PRE, RPN_MAX_ROWS = 8, 16, 512, 4096, 16384    # include/clipself_rpn.h
+RPN_MAX_LEVELS, RPN_MAX_ANCHORS, RPN_MAX_SIDE, RPN_MAX_PRE, RPN_MAX_ROWS = 8, 16, 512, 4096, 16384
 
 
-# include/clipself_conv.h: the detector heads' 3 x 3 convolutions (implicit GEMM, explicit matrix).  An eighth header, an eighth table
+# include/clipself_conv.h: the detector heads' 3 x 3 convolutions (implicit GEMM, explicit matrix)
 CONV_SIGNATURES = {
     "csc_conv3x3": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
     "csc_im2col3x3": (_i, [_vp, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _vp]),
 }
-CONV_MAX_ROWS = (1 << 31) - 512                          # include/clipself_conv.h: N * H * W
+CONV_MAX_ROWS = (1 << 31) - 512                          # N * H * W
 
 
-# include/clipself_bn.h: batch norm (+ ReLU) on channel-last maps, forward and backward.  A ninth header, a ninth table
+# include/clipself_bn.h: batch norm (+ ReLU) on channel-last maps, forward and backward
 BN_SIGNATURES = {
     "csb_row_parts": (_i, [_l, _i]),
     "csb_workspace": (_sz, [_l, _i]),
@@ -166,12 +175,32 @@ BN_SIGNATURES = {
     "csb_bwd_reduce": (_i, [_vp, _l, _i, _vp, _l, _i, _vp, _i, _vp, _vp, _l, _i, _vp]),
     "csb_bwd_apply": (_i, [_vp, _l, _i, _vp, _l, _i, _vp, _i, _vp, _vp, _vp, _l, _i, _l, _i, _vp]),
 }
-BN_MAX_ROWS, BN_MAX_C, BN_MAX_RECORDS, BN_REC_EXTRA, BN_ST_EXTRA = (1 << 31) - 512, 65536, 4096, 4, 4      # include/clipself_bn.h
+BN_MAX_ROWS, BN_MAX_C, BN_MAX_RECORDS, BN_REC_EXTRA, BN_ST_EXTRA = (1 << 31) - 512, 65536, 4096, 4, 4
 
 
-class AttnExtra(ctypes.Structure):
-    """include/clipself_hip.h: cs_attn_extra, the extra query rows of a cs_attn_bwd launch."""
-    _fields_ = [("q", _vp), ("o", _vp), ("dout", _vp), ("lse", _vp), ("allow", _vp), ("dq", _vp), ("Q", _i), ("ldq", _i), ("ldo", _i), ("lddq", _i)]
+# The whole C ABI, one entry per public header: load_library binds these tables and tests/test_cabi_symbols.py holds every one of them,
+# the structs and the macros against the header's text and the built library.  A new header is one more entry here, the include of
+# that header in its source file, and nothing else.
+ABI = {
+    "clipself_hip.h": SIGNATURES, "clipself_det.h": DET_SIGNATURES, "clipself_roi.h": ROI_SIGNATURES, "clipself_assign.h": ASSIGN_SIGNATURES,
+    "clipself_loss.h": LOSS_SIGNATURES, "clipself_mask.h": MASK_SIGNATURES, "clipself_rpn.h": RPN_SIGNATURES, "clipself_conv.h": CONV_SIGNATURES,
+    "clipself_bn.h": BN_SIGNATURES,
+}
+STRUCTS = {"cs_attn_extra": AttnExtra, "csr_level": RoiLevel, "csl_level": LossLevel, "csp_level": RpnLevel}
+MACROS = {
+    "CS_ADAMW_GUARD_HEAD": ADAMW_GUARD_HEAD, "CS_ADAMW_GUARD_SPAN": ADAMW_GUARD_SPAN,
+    "CSD_MAX_BOXES": DET_MAX_BOXES, "CSD_MAX_NUM": DET_MAX_NUM,
+    "CSR_MAX_LEVELS": ROI_MAX_LEVELS, "CSR_MAX_SIDE": ROI_MAX_SIDE, "CSR_MAX_P": ROI_MAX_P, "CSR_MAX_SR": ROI_MAX_SR,
+    "CSA_MAX_ROWS": ASSIGN_MAX_ROWS, "CSA_MAX_GT": ASSIGN_MAX_GT, "CSA_MAX_NUM": ASSIGN_MAX_NUM,
+    "CSL_MAX_LEVELS": LOSS_MAX_LEVELS, "CSL_MAX_ANCHORS": LOSS_MAX_ANCHORS, "CSL_MAX_SIDE": LOSS_MAX_SIDE, "CSL_MAX_ROWS": LOSS_MAX_ROWS,
+    "CSL_MAX_CLASSES": LOSS_MAX_CLASSES,
+    "CSM_MAX_ROWS": MASK_MAX_ROWS, "CSM_MAX_GT": MASK_MAX_GT, "CSM_MAX_SIDE": MASK_MAX_SIDE, "CSM_MAX_MASK": MASK_MAX_MASK,
+    "CSM_MAX_CLASSES": MASK_MAX_CLASSES, "CSM_MAX_IMAGE": MASK_MAX_IMAGE,
+    "CSP_MAX_LEVELS": RPN_MAX_LEVELS, "CSP_MAX_ANCHORS": RPN_MAX_ANCHORS, "CSP_MAX_SIDE": RPN_MAX_SIDE, "CSP_MAX_PRE": RPN_MAX_PRE,
+    "CSP_MAX_ROWS": RPN_MAX_ROWS,
+    "CSC_MAX_ROWS": CONV_MAX_ROWS,
+    "CSB_MAX_ROWS": BN_MAX_ROWS, "CSB_MAX_C": BN_MAX_C, "CSB_MAX_RECORDS": BN_MAX_RECORDS, "CSB_REC_EXTRA": BN_REC_EXTRA, "CSB_ST_EXTRA": BN_ST_EXTRA,
+}
 
 
 def library_path() -> Path:
@@ -198,8 +227,7 @@ def load_library():
                 f"{_LIB_PATH} is missing: build it with clipself_amd/csrc/build.sh (or __graft_entry__.build()). "
                 "There is no CPU fallback for the CLIPSelf hot path.")
         lib = ctypes.CDLL(str(_LIB_PATH))
-        for table in (SIGNATURES, DET_SIGNATURES, ROI_SIGNATURES, ASSIGN_SIGNATURES, LOSS_SIGNATURES, MASK_SIGNATURES, RPN_SIGNATURES,
-                      CONV_SIGNATURES, BN_SIGNATURES):
+        for table in ABI.values():
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
                 fn.restype, fn.argtypes = res, args
@@ -318,6 +346,65 @@ class HipOps:
             if t is not None and not t.is_cuda:
                 raise RuntimeError("HipOps received a non-GPU tensor; the hot path has no CPU fallback")
 
+    # The two layouts the detector headers state, and their workspaces.  ValueError, not assert: these are user-facing limits.
+    @staticmethod
+    def _dense(t, dtype, shape, who):
+        """A dense tensor of this dtype and shape on the device."""
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{who} must be a contiguous {dtype} device tensor {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+    @staticmethod
+    def _rows(t, dtypes, M, C, who, k=None, a=1):
+        """Rows [M, C] (None: any) of one of `dtypes` with last stride 1 -> the row stride: the tensor's, or at least C where M <= 1 leaves
+        it free.  k: the stride must be a multiple of k that holds C (an int, or one per dtype); k=None: the library's to refuse.
+        a: bytes the base is aligned to."""
+        sh, st = t.shape, t.stride()
+        if len(sh) != 2 or t.dtype not in dtypes or (M is not None and sh[0] != M) or (C is not None and sh[1] != C) or (sh[0] and st[1] != 1):
+            raise ValueError(f"{who} must be {' / '.join(str(d) for d in dtypes)} rows [{M}, {C}] with last stride 1, "
+                             f"got {t.dtype} {tuple(sh)} strides {st}")
+        m, c = sh
+        ld = st[0] if m > 1 else max(st[0], c)
+        if k is not None:
+            if k.__class__ is not int:
+                k = k[dtypes.index(t.dtype)]
+            if ld < c or ld % k:
+                raise ValueError(f"{who}: row stride {ld} must be a multiple of {k} that holds {c} columns")
+        if a > 1 and t.data_ptr() % a:
+            raise ValueError(f"{who}: the base must be {a}-byte aligned")
+        return ld
+
+    def _workspace(self, header, need, device, workspace, who):
+        """`need` bytes of 16-byte aligned workspace for an entry point of `header`: the caller's `workspace`, or this object's one
+        grow-only buffer per (header, device) -- so calls that share it must share a stream.  The size is checked either way;
+        need == 0 is the library's answer for shapes outside the header's limits."""
+        if need <= 0:
+            raise ValueError(f"{who}: the shapes are outside the limits of include/{header}")
+        own = workspace is None
+        if own:
+            try:
+                workspace = self._ws[header, device]
+            except (AttributeError, KeyError):
+                pass
+        have = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        if own and have < need:
+            workspace = self.__dict__.setdefault("_ws", {})[header, device] = torch.empty(need, dtype=torch.uint8, device=device)
+            have = need
+        if have < need or workspace.data_ptr() % 16:
+            raise ValueError(f"{who}: workspace holds {have} bytes, {need} (16-byte aligned) are needed")
+        return workspace
+
+    def _size(self, fn, *args):
+        """fn(*args) bytes, remembered: the library's size functions are pure, and a ctypes call costs as much as a wrapper's other checks
+        together (these wrappers run several times per layer and step).  A few thousand integers at the most."""
+        try:
+            return self._sizes[fn, args]
+        except (AttributeError, KeyError):
+            sizes = self.__dict__.setdefault("_sizes", {})
+            if len(sizes) >= 4096:
+                sizes.clear()
+            need = sizes[fn, args] = int(getattr(self.lib, fn)(*args))
+            return need
+
     def empty(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device="cuda")
 
@@ -396,10 +483,8 @@ class HipOps:
         H, W, K = image_u8.shape[0], image_u8.shape[1], boxes.shape[0]
         if out is None:
             out = torch.empty((K, 3, size, size), dtype=torch.float32, device=image_u8.device)
-        need = int(self.lib.cs_crop_resize_workspace(H, K, size))
-        ws = getattr(self, "_crop_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._crop_ws = torch.empty(need, dtype=torch.uint8, device=image_u8.device)
+        need = max(int(self.lib.cs_crop_resize_workspace(H, K, size)), 16)           # K == 0 needs none and is no error
+        ws = self._workspace("clipself_hip.h", need, image_u8.device, None, "crop_resize")
         m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
         self._ok(self.lib.cs_crop_resize_u8(_p(image_u8), H, W, _p(boxes), K, size, int(bool(pad_center)), m3, s3, _p(out), _p(ws),
                                             self._stream()), "cs_crop_resize_u8")
@@ -820,24 +905,23 @@ class HipOps:
 
     # -- detector post-processing (include/clipself_det.h) ------------------------------------------
     def nms_workspace(self, B, Kmax, C_or_G, max_num) -> int:
-        return int(self.lib.csd_nms_workspace(int(B), int(Kmax), int(C_or_G), int(max_num)))
+        return self._size("csd_nms_workspace", int(B), int(Kmax), int(C_or_G), int(max_num))
 
     def nms(self, boxes, scores, starts, Kmax, score_thr, iou_thr, max_num, group=None, G=0, out=None, workspace=None):
         """Score threshold, per-list greedy NMS and the per-image cut (csd_nms): boxes [K, 4], scores [K, C] (foreground columns), starts
         [B + 1] int32 on the device, group [K] int32 with G groups for the RPN form (C == 1).  -> (dets [B, max_num, 5], labels, inds
-        [B, max_num] int32, counts [B] int32): fixed shapes, nothing is read back.  The workspace is cached per shape (pass workspace= to
-        own it): after the first call of a shape the call allocates only its outputs (pass out= to own those too) and never
-        synchronises, which is what stream capture needs (the tests do not capture); calls that share a shape must share a stream."""
+        [B, max_num] int32, counts [B] int32): fixed shapes, nothing is read back.  The workspace is this header's one buffer per device,
+        grown to the largest call so far (pass workspace= to own it): once it is large enough the call allocates only its outputs (pass
+        out= to own those too) and never synchronises, which is what stream capture needs (the tests do not capture); calls that share
+        the buffer must share a stream."""
         self._chk(boxes, scores, starts, group, workspace)
         f32, i32 = torch.float32, torch.int32
+        lds = self._rows(scores, _F32, None, None, "nms: scores")
         K, C = scores.shape
+        ldb = self._rows(boxes, _F32, K, 4, "nms: boxes")
         B = starts.numel() - 1
-        assert boxes.dtype == f32 and boxes.dim() == 2 and boxes.shape == (K, 4) and (K == 0 or boxes.stride(1) == 1)
-        assert scores.dtype == f32 and (K == 0 or scores.stride(1) == 1)
         assert starts.dtype == i32 and starts.is_contiguous() and B >= 1
         assert group is None or (group.dtype == i32 and group.is_contiguous() and group.numel() == K)
-        ldb = boxes.stride(0) if K > 1 else max(boxes.stride(0), 4)
-        lds = scores.stride(0) if K > 1 else max(scores.stride(0), C)
         L = int(G) if group is not None else C
         if out is None:
             dev = boxes.device
@@ -846,13 +930,7 @@ class HipOps:
         dets, labels, inds, counts = out
         assert all(t.is_contiguous() for t in out) and dets.dtype == f32 and labels.dtype == i32 and inds.dtype == i32 and counts.dtype == i32
         assert dets.numel() == B * max_num * 5 and labels.numel() == B * max_num and inds.numel() == B * max_num and counts.numel() == B
-        if workspace is None:
-            need = self.nms_workspace(B, Kmax, L, max_num)
-            key = (B, int(Kmax), L, int(max_num), boxes.device)
-            cache = self.__dict__.setdefault("_nms_ws", {})
-            workspace = cache.get(key)
-            if workspace is None and need > 0:
-                workspace = cache[key] = torch.empty(need, dtype=torch.uint8, device=boxes.device)
+        workspace = self._workspace("clipself_det.h", self.nms_workspace(B, Kmax, L, max_num), boxes.device, workspace, "nms")
         self._ok(self.lib.csd_nms(_p(boxes), ldb, _p(scores), lds, C, _p(starts), _p(group), int(G), K, B, int(Kmax), float(score_thr),
                                   float(iou_thr), int(max_num), _p(dets), _p(labels), _p(inds), _p(counts), _p(workspace), self._stream()),
                  "csd_nms")
@@ -866,46 +944,42 @@ class HipOps:
         self._chk(rois, deltas, out, starts, max_shape, scale)
         f32 = torch.float32
         K = rois.shape[0]
-        for t in (rois, deltas, out):
-            assert t.dtype == f32 and t.dim() == 2 and t.shape == (K, 4) and (K == 0 or t.stride(1) == 1)
+        ldr = self._rows(rois, _F32, K, 4, "delta2bbox: rois")
+        ldd = self._rows(deltas, _F32, K, 4, "delta2bbox: deltas")
+        ldo = self._rows(out, _F32, K, 4, "delta2bbox: out")
         B = 0
         if max_shape is not None or scale is not None:
             assert starts is not None and starts.dtype == torch.int32 and starts.is_contiguous()
             B = starts.numel() - 1
             assert max_shape is None or (max_shape.dtype == f32 and max_shape.is_contiguous() and tuple(max_shape.shape) == (B, 2))
             assert scale is None or (scale.dtype == f32 and scale.is_contiguous() and tuple(scale.shape) == (B, 4))
-        ld = lambda t: t.stride(0) if K > 1 else max(t.stride(0), 4)
         m4, s4 = (_f * 4)(*[float(v) for v in means]), (_f * 4)(*[float(v) for v in stds])
-        self._ok(self.lib.csd_delta2bbox(_p(rois), ld(rois), _p(deltas), ld(deltas), _p(starts), B, K, m4, s4, float(wh_ratio_clip),
-                                         _p(max_shape), _p(scale), _p(out), ld(out), self._stream()), "csd_delta2bbox")
+        self._ok(self.lib.csd_delta2bbox(_p(rois), ldr, _p(deltas), ldd, _p(starts), B, K, m4, s4, float(wh_ratio_clip),
+                                         _p(max_shape), _p(scale), _p(out), ldo, self._stream()), "csd_delta2bbox")
         return out
 
     # -- detector training targets (include/clipself_assign.h) -----------------------------------------
     def assign_workspace(self, B, Nmax, Gmax, num=1) -> int:
-        return int(self.lib.csa_workspace(int(B), int(Nmax), int(Gmax), int(num)))
+        return self._size("csa_workspace", int(B), int(Nmax), int(Gmax), int(num))
 
-    @staticmethod
-    def _assign_layout(boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax):
-        """The checks the three csa_ wrappers share -> (K, ldb, Gtot, ldg).  ValueError, not assert: these are user-facing limits."""
+    def _assign_layout(self, boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax):
+        """The checks the three csa_ wrappers share -> (K, ldb, Gtot, ldg)."""
         f32, i32 = torch.float32, torch.int32
-        if boxes.dtype != f32 or boxes.dim() != 2 or boxes.shape[1] != 4 or (boxes.shape[0] and boxes.stride(1) != 1):
-            raise ValueError(f"boxes must be fp32 [K, 4] with last stride 1, got {boxes.dtype} {tuple(boxes.shape)} strides {boxes.stride()}")
-        if gt_boxes.dtype != f32 or gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4 or (gt_boxes.shape[0] and gt_boxes.stride(1) != 1):
-            raise ValueError(f"gt_boxes must be fp32 [Gtot, 4] with last stride 1, got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
+        ldb, ldg = self._rows(boxes, _F32, None, 4, "boxes"), self._rows(gt_boxes, _F32, None, 4, "gt_boxes")
         if gt_starts.dtype != i32 or not gt_starts.is_contiguous() or gt_starts.numel() != B + 1:
             raise ValueError(f"gt_starts must be contiguous int32 [B + 1] = [{B + 1}], got {gt_starts.dtype} {tuple(gt_starts.shape)}")
         if starts is not None and (starts.dtype != i32 or not starts.is_contiguous() or starts.numel() != B + 1):
             raise ValueError(f"starts must be None (shared rows) or contiguous int32 [B + 1] = [{B + 1}], got {starts.dtype} {tuple(starts.shape)}")
         if not (1 <= B <= 65535 and 0 <= Nmax <= ASSIGN_MAX_ROWS and 0 <= Gmax <= ASSIGN_MAX_GT):
             raise ValueError(f"limits: 1 <= B <= 65535, 0 <= Nmax <= {ASSIGN_MAX_ROWS}, 0 <= Gmax <= {ASSIGN_MAX_GT} (B = {B}, Nmax = {Nmax}, Gmax = {Gmax})")
-        K, Gtot = boxes.shape[0], gt_boxes.shape[0]
-        return K, (boxes.stride(0) if K > 1 else max(boxes.stride(0), 4)), Gtot, (gt_boxes.stride(0) if Gtot > 1 else max(gt_boxes.stride(0), 4))
+        return boxes.shape[0], ldb, gt_boxes.shape[0], ldg
 
     def assign(self, boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax, pos_iou_thr, neg_iou_thr, min_pos_iou=0.0, match_low_quality=True,
                gt_max_assign_all=True, gt_prefix=False, valid=None, out=None, workspace=None):
         """MaxIoUAssigner.assign for B images in one call (csa_assign): boxes [K, 4] grouped by starts [B + 1] int32 (None: all images share
         the K rows), gt_boxes [Gtot, 4] grouped by gt_starts, valid [K] uint8 or None; neg_iou_thr a float or (lo, hi).
-        -> (gt_inds [B, Nmax] int32, max_overlaps [B, Nmax] fp32); nothing is read back.  The workspace is cached per shape."""
+        -> (gt_inds [B, Nmax] int32, max_overlaps [B, Nmax] fp32); nothing is read back.  The workspace is this header's one
+        buffer per device (pass workspace= to own it); calls that share it must share a stream."""
         self._chk(boxes, starts, gt_boxes, gt_starts, valid, workspace)
         B, Nmax, Gmax = int(B), int(Nmax), int(Gmax)
         K, ldb, Gtot, ldg = self._assign_layout(boxes, starts, gt_boxes, gt_starts, B, Nmax, Gmax)
@@ -918,12 +992,7 @@ class HipOps:
         if not (gt_inds.dtype == torch.int32 and max_overlaps.dtype == torch.float32 and gt_inds.is_contiguous() and max_overlaps.is_contiguous()
                 and gt_inds.numel() == B * Nmax and max_overlaps.numel() == B * Nmax):
             raise ValueError("out must be (int32 [B, Nmax], fp32 [B, Nmax]), contiguous")
-        if workspace is None:
-            key = (B, Gmax, boxes.device)
-            cache = self.__dict__.setdefault("_assign_ws", {})
-            workspace = cache.get(key)
-            if workspace is None:
-                workspace = cache[key] = torch.empty(self.assign_workspace(B, Nmax, Gmax), dtype=torch.uint8, device=boxes.device)
+        workspace = self._workspace("clipself_assign.h", self.assign_workspace(B, Nmax, Gmax), boxes.device, workspace, "assign")
         self._ok(self.lib.csa_assign(_p(boxes), ldb, _p(starts), K, _p(gt_boxes), ldg, _p(gt_starts), Gtot, _p(valid), B, Nmax, Gmax,
                                      float(pos_iou_thr), float(lo), float(hi), float(min_pos_iou), int(bool(match_low_quality)),
                                      int(bool(gt_max_assign_all)), int(bool(gt_prefix)), _p(gt_inds), _p(max_overlaps), _p(workspace),
@@ -1006,11 +1075,6 @@ class HipOps:
         return (labels, label_weights, bt, bw) if sel is None else (rois, labels, label_weights, bt, bw)
 
     # -- detector losses (include/clipself_loss.h) ------------------------------------------------------
-    @staticmethod
-    def _loss_dense(t, dtype, shape, who):
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError(f"{who} must be a contiguous {dtype} device tensor {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-
     def _loss_levels(self, cls_scores, bbox_preds, dcls=None, dreg=None):
         L = len(cls_scores)
         if not (1 <= L <= LOSS_MAX_LEVELS and len(bbox_preds) == L):
@@ -1021,11 +1085,11 @@ class HipOps:
             if c.dim() != 4:
                 raise ValueError(f"rpn_loss: level {l}: cls must be [B, A, h, w], got {tuple(c.shape)}")
             h, w = c.shape[2], c.shape[3]
-            self._loss_dense(c, torch.float32, (B, A, h, w), f"rpn_loss: level {l}: cls")
-            self._loss_dense(r, torch.float32, (B, 4 * A, h, w), f"rpn_loss: level {l}: reg")
+            self._dense(c, torch.float32, (B, A, h, w), f"rpn_loss: level {l}: cls")
+            self._dense(r, torch.float32, (B, 4 * A, h, w), f"rpn_loss: level {l}: reg")
             if dcls is not None:
-                self._loss_dense(dcls[l], torch.float32, (B, A, h, w), f"rpn_loss: level {l}: dcls")
-                self._loss_dense(dreg[l], torch.float32, (B, 4 * A, h, w), f"rpn_loss: level {l}: dreg")
+                self._dense(dcls[l], torch.float32, (B, A, h, w), f"rpn_loss: level {l}: dcls")
+                self._dense(dreg[l], torch.float32, (B, 4 * A, h, w), f"rpn_loss: level {l}: dreg")
             arr[l] = LossLevel(c.data_ptr(), r.data_ptr(), None if dcls is None else dcls[l].data_ptr(), None if dreg is None else dreg[l].data_ptr(),
                                int(h), int(w))
             N += h * w * A
@@ -1037,18 +1101,6 @@ class HipOps:
             return int(self.lib.csl_workspace(None, 0, 1, 1, int(R)))
         arr, L, B, A, _ = self._loss_levels(cls_scores, bbox_preds)
         return int(self.lib.csl_workspace(arr, L, B, A, int(R)))
-
-    def _loss_ws(self, need, device, workspace):
-        if need <= 0:
-            raise ValueError("the shapes are outside the limits of include/clipself_loss.h")
-        if workspace is None:
-            cache = self.__dict__.setdefault("_loss_ws_cache", {})
-            workspace = cache.get(device)
-            if workspace is None or workspace.numel() < need:
-                workspace = cache[device] = torch.empty(need, dtype=torch.uint8, device=device)
-        if workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace holds {workspace.numel() * workspace.element_size()} bytes, {need} are needed")
-        return workspace
 
     def rpn_loss(self, cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factor, grad=True, out=None, workspace=None):
         """RPNHead.loss for all levels and images in one call (csl_rpn_loss).  cls_scores[l] [B, A, h, w], bbox_preds[l] [B, 4A, h, w];
@@ -1066,14 +1118,14 @@ class HipOps:
         if (dcls is None) != (dreg is None):
             raise ValueError("rpn_loss: dcls and dreg are given together or both None")
         arr, L, B, A, N = self._loss_levels(cls_scores, bbox_preds, dcls, dreg)
-        self._loss_dense(labels, torch.int32, (B, N), "rpn_loss: labels")
-        self._loss_dense(label_weights, torch.float32, (B, N), "rpn_loss: label_weights")
-        self._loss_dense(bbox_targets, torch.float32, (B, N, 4), "rpn_loss: bbox_targets")
-        self._loss_dense(bbox_weights, torch.float32, (B, N, 4), "rpn_loss: bbox_weights")
-        self._loss_dense(losses, torch.float32, (L, 2), "rpn_loss: losses")
+        self._dense(labels, torch.int32, (B, N), "rpn_loss: labels")
+        self._dense(label_weights, torch.float32, (B, N), "rpn_loss: label_weights")
+        self._dense(bbox_targets, torch.float32, (B, N, 4), "rpn_loss: bbox_targets")
+        self._dense(bbox_weights, torch.float32, (B, N, 4), "rpn_loss: bbox_weights")
+        self._dense(losses, torch.float32, (L, 2), "rpn_loss: losses")
         if avg_factor.dtype != torch.float32 or avg_factor.numel() != 1:
             raise ValueError(f"rpn_loss: avg_factor must be a device fp32 scalar, got {avg_factor.dtype} {tuple(avg_factor.shape)}")
-        ws = self._loss_ws(int(self.lib.csl_workspace(arr, L, B, A, 0)), dev, workspace)
+        ws = self._workspace("clipself_loss.h", int(self.lib.csl_workspace(arr, L, B, A, 0)), dev, workspace, "rpn_loss")
         self._ok(self.lib.csl_rpn_loss(arr, L, B, A, _p(labels), _p(label_weights), _p(bbox_targets), _p(bbox_weights), _p(avg_factor), _p(losses),
                                        _p(ws), self._stream()), "csl_rpn_loss")
         return losses, dcls, dreg
@@ -1085,17 +1137,15 @@ class HipOps:
         (None: max(count(label_weights > 0), 1) on the device).  -> (out4 = (loss_cls, acc, loss_bbox, avg) [4], dcls [R, C1] with
         cls_score's row stride, dbbox [R, 4]), the gradients None with grad=False.  out: the same triple, to own the outputs."""
         self._chk(cls_score, labels, label_weights, bbox_pred, bbox_targets, bbox_weights, class_weight, avg_factor)
-        if cls_score.dim() != 2 or cls_score.dtype != torch.float32 or (cls_score.numel() and cls_score.stride(1) != 1):
-            raise ValueError(f"bbox_head_loss: cls_score must be fp32 [R, C1] with last stride 1, got {cls_score.dtype} {tuple(cls_score.shape)}")
-        R, C1 = cls_score.shape
-        ldc = max(cls_score.stride(0), C1) if R > 0 else C1
         dev, f32 = cls_score.device, torch.float32
-        self._loss_dense(labels, torch.int32, (R,), "bbox_head_loss: labels")
-        self._loss_dense(label_weights, f32, (R,), "bbox_head_loss: label_weights")
+        ldc = self._rows(cls_score, _F32, None, None, "bbox_head_loss: cls_score")
+        R, C1 = cls_score.shape
+        self._dense(labels, torch.int32, (R,), "bbox_head_loss: labels")
+        self._dense(label_weights, f32, (R,), "bbox_head_loss: label_weights")
         for t, who in ((bbox_pred, "bbox_pred"), (bbox_targets, "bbox_targets"), (bbox_weights, "bbox_weights")):
-            self._loss_dense(t, f32, (R, 4), "bbox_head_loss: " + who)
+            self._dense(t, f32, (R, 4), "bbox_head_loss: " + who)
         if class_weight is not None:
-            self._loss_dense(class_weight, f32, (C1,), "bbox_head_loss: class_weight")
+            self._dense(class_weight, f32, (C1,), "bbox_head_loss: class_weight")
         if avg_factor is not None and (avg_factor.dtype != f32 or avg_factor.numel() != 1):
             raise ValueError(f"bbox_head_loss: avg_factor must be a device fp32 scalar or None, got {avg_factor.dtype} {tuple(avg_factor.shape)}")
         if out is None:
@@ -1104,13 +1154,13 @@ class HipOps:
             dbbox = torch.empty(R, 4, dtype=f32, device=dev) if grad else None
         else:
             out4, dcls, dbbox = out
-        self._loss_dense(out4, f32, (4,), "bbox_head_loss: out")
+        self._dense(out4, f32, (4,), "bbox_head_loss: out")
         if dcls is not None:
             if dcls.dtype != f32 or tuple(dcls.shape) != (R, C1) or not dcls.is_cuda or (R > 0 and dcls.stride(1) != 1) or (R > 1 and dcls.stride(0) != ldc):
                 raise ValueError(f"bbox_head_loss: dcls must be fp32 [R, C1] with cls_score's strides ({ldc}, 1), got {tuple(dcls.shape)} {dcls.stride()}")
         if dbbox is not None:
-            self._loss_dense(dbbox, f32, (R, 4), "bbox_head_loss: dbbox")
-        ws = self._loss_ws(int(self.lib.csl_workspace(None, 0, 1, 1, R)), dev, workspace)
+            self._dense(dbbox, f32, (R, 4), "bbox_head_loss: dbbox")
+        ws = self._workspace("clipself_loss.h", int(self.lib.csl_workspace(None, 0, 1, 1, R)), dev, workspace, "bbox_head_loss")
         self._ok(self.lib.csl_bbox_head_loss(_p(cls_score), ldc, _p(labels), _p(label_weights), _p(class_weight), _p(bbox_pred), _p(bbox_targets),
                                              _p(bbox_weights), R, C1, int(bg_label), _p(avg_factor), _p(out4), _p(dcls), _p(dbbox), _p(ws),
                                              self._stream()), "csl_bbox_head_loss")
@@ -1136,8 +1186,8 @@ class HipOps:
             h, w = int(c.shape[2]), int(c.shape[3])
             if not (1 <= h <= RPN_MAX_SIDE and 1 <= w <= RPN_MAX_SIDE):
                 raise ValueError(f"rpn_select: level {l}: h = {h}, w = {w} must be in [1, {RPN_MAX_SIDE}]")
-            self._loss_dense(c, torch.float32, (B, A, h, w), f"rpn_select: level {l}: cls")
-            self._loss_dense(r, torch.float32, (B, 4 * A, h, w), f"rpn_select: level {l}: reg")
+            self._dense(c, torch.float32, (B, A, h, w), f"rpn_select: level {l}: cls")
+            self._dense(r, torch.float32, (B, 4 * A, h, w), f"rpn_select: level {l}: reg")
             arr[l] = RpnLevel(c.data_ptr(), r.data_ptr(), h, w)
             N += h * w * A
             Ktot += min(nms_pre, h * w * A)
@@ -1167,28 +1217,19 @@ class HipOps:
         if lda < 4:
             raise ValueError(f"rpn_select: the row stride of anchors is {lda}, at least 4 is needed")
         if max_shape is not None:
-            self._loss_dense(max_shape, f32, (B, 2), "rpn_select: max_shape")
+            self._dense(max_shape, f32, (B, 2), "rpn_select: max_shape")
         if out is None:
             out = (torch.empty(B * Ktot, 4, dtype=f32, device=dev), torch.empty(B * Ktot, dtype=f32, device=dev),
                    torch.empty(B * Ktot, dtype=i32, device=dev), torch.empty(B * Ktot, dtype=i32, device=dev),
                    torch.empty(B + 1, dtype=i32, device=dev))
         boxes, scores, group, anchor_inds, starts = out
-        self._loss_dense(boxes, f32, (B * Ktot, 4), "rpn_select: boxes")
-        self._loss_dense(scores, f32, (B * Ktot,), "rpn_select: scores")
-        self._loss_dense(group, i32, (B * Ktot,), "rpn_select: group")
+        self._dense(boxes, f32, (B * Ktot, 4), "rpn_select: boxes")
+        self._dense(scores, f32, (B * Ktot,), "rpn_select: scores")
+        self._dense(group, i32, (B * Ktot,), "rpn_select: group")
         if anchor_inds is not None:
-            self._loss_dense(anchor_inds, i32, (B * Ktot,), "rpn_select: anchor_inds")
-        self._loss_dense(starts, i32, (B + 1,), "rpn_select: starts")
-        need = int(self.lib.csp_workspace(arr, L, B, A, int(nms_pre)))
-        if need <= 0:
-            raise ValueError("rpn_select: the shapes are outside the limits of include/clipself_rpn.h")
-        if workspace is None:
-            cache = self.__dict__.setdefault("_rpn_ws_cache", {})
-            workspace = cache.get(dev)
-            if workspace is None or workspace.numel() < need:
-                workspace = cache[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-        if workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"rpn_select: workspace holds {workspace.numel() * workspace.element_size()} bytes, {need} are needed")
+            self._dense(anchor_inds, i32, (B * Ktot,), "rpn_select: anchor_inds")
+        self._dense(starts, i32, (B + 1,), "rpn_select: starts")
+        workspace = self._workspace("clipself_rpn.h", int(self.lib.csp_workspace(arr, L, B, A, int(nms_pre))), dev, workspace, "rpn_select")
         m4, s4 = (_f * 4)(*[float(v) for v in means]), (_f * 4)(*[float(v) for v in stds])
         self._ok(self.lib.csp_select(arr, L, B, A, _p(anchors), lda, int(nms_pre), m4, s4, float(wh_ratio_clip), _p(max_shape),
                                      float(min_bbox_size), _p(boxes), _p(scores), _p(group), _p(anchor_inds), _p(starts), _p(workspace),
@@ -1196,16 +1237,6 @@ class HipOps:
         return boxes, scores, group, anchor_inds, starts
 
     # -- 3 x 3 convolutions of the detector heads (include/clipself_conv.h) ---------------------------------
-    @staticmethod
-    def _conv_map(t, N, H, W, who):
-        """A map as the header states it: bf16 rows [N*H*W, C], last stride 1, a row stride that is a multiple of 8, 16-byte aligned."""
-        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[0] != N * H * W or t.stride(1) != 1:
-            raise ValueError(f"{who} must be bf16 rows [N*H*W = {N * H * W}, C] with last stride 1, got {t.dtype} {tuple(t.shape)} {t.stride()}")
-        ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-        if ld < t.shape[1] or ld % 8 or t.data_ptr() % 16:
-            raise ValueError(f"{who}: row stride {ld} must be a multiple of 8 that holds {t.shape[1]} channels, the base 16-byte aligned")
-        return ld
-
     def conv3x3(self, x, Wg, y, bias, N, H, W):
         """y[p, co] = bias[co] + sum_{t, ci} x[p shifted by tap t, ci] * Wg[co, t*Cin + ci] (csc_conv3x3): Conv2d(Cin, Cout, 3, padding=1)
         on channel-last rows.  x bf16 [N*H*W, Cin] (row stride % 8 == 0), Wg bf16 [Cout, 9*Cin], bias fp32 [Cout] or None, y fp32 or bf16
@@ -1214,18 +1245,14 @@ class HipOps:
         N, H, W = int(N), int(H), int(W)
         if min(N, H, W) < 1 or N * H * W > CONV_MAX_ROWS:
             raise ValueError(f"conv3x3: 1 <= N*H*W <= {CONV_MAX_ROWS} (N = {N}, H = {H}, W = {W})")
-        ldx = self._conv_map(x, N, H, W, "conv3x3: x")
+        ldx = self._rows(x, (torch.bfloat16,), N * H * W, None, "conv3x3: x", 8, 16)
         Cin = x.shape[1]
         if Wg.dtype != torch.bfloat16 or Wg.dim() != 2 or Wg.shape[1] != 9 * Cin or Wg.stride(1) != 1 or Wg.stride(0) % 8 or Wg.data_ptr() % 16:
             raise ValueError(f"conv3x3: Wg must be bf16 [Cout, 9*Cin = {9 * Cin}] with 16-byte aligned rows, got {Wg.dtype} {tuple(Wg.shape)}")
         Cout = Wg.shape[0]
         if Cin % 64 or Cout % 8:
             raise ValueError(f"conv3x3: outside the kernel's coverage (Cin % 64 == 0, Cout % 8 == 0): Cin = {Cin}, Cout = {Cout}")
-        if y.dtype not in (torch.float32, torch.bfloat16) or y.dim() != 2 or tuple(y.shape) != (N * H * W, Cout) or y.stride(1) != 1:
-            raise ValueError(f"conv3x3: y must be fp32 / bf16 rows [{N * H * W}, {Cout}] with last stride 1, got {y.dtype} {tuple(y.shape)}")
-        ldy = y.stride(0) if y.shape[0] > 1 else max(y.stride(0), Cout)
-        if ldy < Cout or ldy % 4 or y.data_ptr() % 16:
-            raise ValueError(f"conv3x3: y's row stride {ldy} must be a multiple of 4 that holds {Cout} channels, the base 16-byte aligned")
+        ldy = self._rows(y, _F32_BF16, N * H * W, Cout, "conv3x3: y", 4, 16)
         if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,) or not bias.is_contiguous() or bias.data_ptr() % 16):
             raise ValueError(f"conv3x3: bias must be contiguous fp32 [{Cout}], 16-byte aligned")
         rc = self.lib.csc_conv3x3(_p(x), ldx, _p(Wg), max(Wg.stride(0), 9 * Cin), _p(bias), _p(y), ldy, _dt(y), N, H, W, Cin, Cout, self._stream())
@@ -1241,16 +1268,12 @@ class HipOps:
         N, H, W, row0 = int(N), int(H), int(W), int(row0)
         if min(N, H, W) < 1 or N * H * W > CONV_MAX_ROWS:
             raise ValueError(f"im2col3x3: 1 <= N*H*W <= {CONV_MAX_ROWS} (N = {N}, H = {H}, W = {W})")
-        ldx = self._conv_map(x, N, H, W, "im2col3x3: x")
+        ldx = self._rows(x, (torch.bfloat16,), N * H * W, None, "im2col3x3: x", 8, 16)
         Cin = x.shape[1]
         if Cin % 8:
             raise ValueError(f"im2col3x3: outside the kernel's coverage (Cin % 8 == 0): Cin = {Cin}")
-        if cols.dtype != torch.bfloat16 or cols.dim() != 2 or cols.shape[1] != 9 * Cin or cols.stride(1) != 1:
-            raise ValueError(f"im2col3x3: cols must be bf16 [rows, 9*Cin = {9 * Cin}] with last stride 1, got {cols.dtype} {tuple(cols.shape)}")
+        ldc = self._rows(cols, (torch.bfloat16,), None, 9 * Cin, "im2col3x3: cols", 8, 16)
         rows = cols.shape[0]
-        ldc = cols.stride(0) if rows > 1 else max(cols.stride(0), 9 * Cin)
-        if ldc < 9 * Cin or ldc % 8 or cols.data_ptr() % 16:
-            raise ValueError(f"im2col3x3: cols' row stride {ldc} must be a multiple of 8 that holds {9 * Cin} columns, the base 16-byte aligned")
         if not (0 <= row0 and row0 + rows <= N * H * W):
             raise ValueError(f"im2col3x3: rows [{row0}, {row0 + rows}) outside the map's {N * H * W} rows")
         rc = self.lib.csc_im2col3x3(_p(x), ldx, _p(cols), ldc, row0, rows, N, H, W, Cin, self._stream())
@@ -1259,16 +1282,6 @@ class HipOps:
         self._ok(rc, "csc_im2col3x3")
 
     # -- batch norm (+ ReLU) on channel-last maps (include/clipself_bn.h) --------------------------------
-    @staticmethod
-    def _bn_map(t, M, C, who):
-        """A map as the header states it: fp32 / bf16 rows [M, C], last stride 1, row stride % 4 (fp32) or % 8 (bf16), 16-byte aligned."""
-        if t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 2 or tuple(t.shape) != (M, C) or t.stride(1) != 1:
-            raise ValueError(f"{who} must be fp32 / bf16 rows [{M}, {C}] with last stride 1, got {t.dtype} {tuple(t.shape)} {t.stride()}")
-        ld = t.stride(0) if M > 1 else max(t.stride(0), C)
-        if ld < C or ld % (8 if t.dtype == torch.bfloat16 else 4) or t.data_ptr() % 16:
-            raise ValueError(f"{who}: row stride {ld} must be a multiple of 8 (bf16) / 4 (fp32) that holds {C} channels, the base 16-byte aligned")
-        return ld
-
     @staticmethod
     def _bn_shape(x, who):
         if x.dim() != 2:
@@ -1302,30 +1315,15 @@ class HipOps:
 
     def bn_workspace(self, M, C) -> int:
         """Bytes of per-part partial sums (csb_workspace) that bn_stats and bn_bwd_reduce need for a map of M rows and C channels."""
-        sizes = self.__dict__.setdefault("_bn_ws_sizes", {})
-        need = sizes.get((M, C))
-        if need is None:
-            need = sizes[(M, C)] = int(self.lib.csb_workspace(int(M), int(C)))
-        return need
-
-    def _bn_ws(self, ws, M, C, who, dev):
-        need = self.bn_workspace(M, C)
-        if ws is None:
-            cache = self.__dict__.setdefault("_bn_ws_cache", {})
-            ws = cache.get(dev)
-            if ws is None or ws.numel() < need:
-                ws = cache[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-        if ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
-            raise ValueError(f"{who}: workspace holds {ws.numel() * ws.element_size()} bytes, {need} (16-byte aligned) are needed")
-        return ws
+        return self._size("csb_workspace", int(M), int(C))
 
     def bn_stats(self, x, rec, ws=None):
         """This rank's record of the map x [M, C] (csb_stats): rec fp32 [2*C + 4] = mean | M2 = sum (x - mean)^2 | the row count as int32 bits."""
         self._chk(x, rec, ws)
         M, C = self._bn_shape(x, "bn_stats")
-        ldx = self._bn_map(x, M, C, "bn_stats: x")
+        ldx = self._rows(x, _F32_BF16, M, C, "bn_stats: x", (4, 8), 16)
         self._bn_vec(rec, 2 * C + BN_REC_EXTRA, "bn_stats: rec")
-        ws = self._bn_ws(ws, M, C, "bn_stats", x.device)
+        ws = self._workspace("clipself_bn.h", self._size("csb_workspace", M, C), x.device, ws, "bn_stats")
         self._bn_rc(self.lib.csb_stats(_p(x), ldx, _dt(x), M, C, _p(rec), _p(ws), self._bn_stream(x)), "csb_stats")
 
     def bn_finalize(self, recs, C, gamma, beta, eps, momentum, running_mean, running_var, st):
@@ -1365,7 +1363,8 @@ class HipOps:
         """y = act(fmaf(x, scale[c], shift[c])) (csb_apply): x, y fp32 / bf16 [M, C], st from bn_finalize, act 0 = none, 1 = ReLU."""
         self._chk(x, st, y)
         M, C = self._bn_shape(x, "bn_apply")
-        ldx, ldy = self._bn_map(x, M, C, "bn_apply: x"), self._bn_map(y, M, C, "bn_apply: y")
+        ldx = self._rows(x, _F32_BF16, M, C, "bn_apply: x", (4, 8), 16)
+        ldy = self._rows(y, _F32_BF16, M, C, "bn_apply: y", (4, 8), 16)
         self._bn_vec(st, 4 * C + BN_ST_EXTRA, "bn_apply: st")
         self._bn_rc(self.lib.csb_apply(_p(x), ldx, _dt(x), _p(st), self._bn_act(act), _p(y), ldy, _dt(y), M, C, self._bn_stream(x)), "csb_apply")
 
@@ -1373,10 +1372,11 @@ class HipOps:
         """sums fp32 [2*C] = sum g | sum g * xhat over the rows (csb_bwd_reduce), g = dy under the ReLU mask recomputed from x and st."""
         self._chk(dy, x, st, sums, ws)
         M, C = self._bn_shape(x, "bn_bwd_reduce")
-        lddy, ldx = self._bn_map(dy, M, C, "bn_bwd_reduce: dy"), self._bn_map(x, M, C, "bn_bwd_reduce: x")
+        lddy = self._rows(dy, _F32_BF16, M, C, "bn_bwd_reduce: dy", (4, 8), 16)
+        ldx = self._rows(x, _F32_BF16, M, C, "bn_bwd_reduce: x", (4, 8), 16)
         self._bn_vec(st, 4 * C + BN_ST_EXTRA, "bn_bwd_reduce: st")
         self._bn_vec(sums, 2 * C, "bn_bwd_reduce: sums")
-        ws = self._bn_ws(ws, M, C, "bn_bwd_reduce", x.device)
+        ws = self._workspace("clipself_bn.h", self._size("csb_workspace", M, C), x.device, ws, "bn_bwd_reduce")
         self._bn_rc(self.lib.csb_bwd_reduce(_p(dy), lddy, _dt(dy), _p(x), ldx, _dt(x), _p(st), self._bn_act(act), _p(sums), _p(ws), M, C,
                                             self._bn_stream(x)), "csb_bwd_reduce")
 
@@ -1385,7 +1385,9 @@ class HipOps:
         evaluation-mode state.  gamma fp32 [C] or None."""
         self._chk(dy, x, st, sums, gamma, dx)
         M, C = self._bn_shape(x, "bn_bwd_apply")
-        lddy, ldx, lddx = (self._bn_map(t, M, C, f"bn_bwd_apply: {n}") for t, n in ((dy, "dy"), (x, "x"), (dx, "dx")))
+        lddy = self._rows(dy, _F32_BF16, M, C, "bn_bwd_apply: dy", (4, 8), 16)
+        ldx = self._rows(x, _F32_BF16, M, C, "bn_bwd_apply: x", (4, 8), 16)
+        lddx = self._rows(dx, _F32_BF16, M, C, "bn_bwd_apply: dx", (4, 8), 16)
         self._bn_vec(st, 4 * C + BN_ST_EXTRA, "bn_bwd_apply: st")
         self._bn_vec(sums, 2 * C, "bn_bwd_apply: sums")
         self._bn_vec(gamma, C, "bn_bwd_apply: gamma", optional=True)
@@ -1395,7 +1397,7 @@ class HipOps:
     # -- detector mask branch (include/clipself_mask.h) --------------------------------------------------
     def mask_workspace(self, R) -> int:
         """Bytes of workspace (csm_workspace) for mask_loss on R rows; 0 outside the limits."""
-        return int(self.lib.csm_workspace(int(R)))
+        return self._size("csm_workspace", int(R))
 
     def mask_target(self, rois, gt_rows, masks, M, soft=False, out=None):
         """mask_target / BitmapMasks.crop_and_resize (csm_mask_target).  rois [R, 5] fp32 contiguous (image, x0, y0, x1, y1), gt_rows [R]
@@ -1403,8 +1405,8 @@ class HipOps:
         passed on).  -> targets [R, M, M], uint8 (t >= 0.5) or, with soft=True, fp32.  Nothing is read back."""
         self._chk(rois, gt_rows, masks)
         R, M = rois.shape[0], int(M)
-        self._loss_dense(rois, torch.float32, (R, 5), "mask_target: rois")
-        self._loss_dense(gt_rows, torch.int32, (R,), "mask_target: gt_rows")
+        self._dense(rois, torch.float32, (R, 5), "mask_target: rois")
+        self._dense(gt_rows, torch.int32, (R,), "mask_target: gt_rows")
         if masks.dtype != torch.uint8 or masks.dim() != 3 or (masks.numel() and masks.stride(2) != 1):
             raise ValueError(f"mask_target: masks must be uint8 [Gtot, H, W] with last stride 1, got {masks.dtype} {tuple(masks.shape)}")
         Gtot, H, W = masks.shape
@@ -1416,7 +1418,7 @@ class HipOps:
         dt = torch.float32 if soft else torch.uint8
         if out is None:
             out = torch.empty(R, M, M, dtype=dt, device=rois.device)
-        self._loss_dense(out, dt, (R, M, M), "mask_target: out")
+        self._dense(out, dt, (R, M, M), "mask_target: out")
         self._ok(self.lib.csm_mask_target(_p(rois), _p(gt_rows), R, _p(masks), Gtot, H, W, ldm, plane, M, int(bool(soft)), _p(out),
                                           self._stream()), "csm_mask_target")
         return out
@@ -1431,25 +1433,22 @@ class HipOps:
             raise ValueError(f"mask_loss: pred must be [R, C, M, M], got {tuple(pred.shape)}")
         R, C, M, _ = pred.shape
         f32 = torch.float32
-        self._loss_dense(pred, f32, (R, C, M, M), "mask_loss: pred")
+        self._dense(pred, f32, (R, C, M, M), "mask_loss: pred")
         if labels is not None:
-            self._loss_dense(labels, torch.int32, (R,), "mask_loss: labels")
+            self._dense(labels, torch.int32, (R,), "mask_loss: labels")
         if targets.dtype not in (torch.uint8, f32):
             raise ValueError(f"mask_loss: targets must be uint8 or fp32, got {targets.dtype}")
-        self._loss_dense(targets, targets.dtype, (R, M, M), "mask_loss: targets")
-        self._loss_dense(row_weights, f32, (R,), "mask_loss: row_weights")
+        self._dense(targets, targets.dtype, (R, M, M), "mask_loss: targets")
+        self._dense(row_weights, f32, (R,), "mask_loss: row_weights")
         dev = pred.device
         if out is None:
             out2, dpred = torch.empty(2, dtype=f32, device=dev), (torch.empty_like(pred) if grad else None)
         else:
             out2, dpred = out
-        self._loss_dense(out2, f32, (2,), "mask_loss: out")
+        self._dense(out2, f32, (2,), "mask_loss: out")
         if dpred is not None:
-            self._loss_dense(dpred, f32, (R, C, M, M), "mask_loss: dpred")
-        need = self.mask_workspace(R)
-        if need <= 0 or R * C * M * M >= 1 << 31:
-            raise ValueError("mask_loss: the shapes are outside the limits of include/clipself_mask.h")
-        ws = self._loss_ws(need, dev, workspace)
+            self._dense(dpred, f32, (R, C, M, M), "mask_loss: dpred")
+        ws = self._workspace("clipself_mask.h", self.mask_workspace(R) if R * C * M * M < 1 << 31 else 0, dev, workspace, "mask_loss")
         self._ok(self.lib.csm_mask_loss(_p(pred), _p(labels), _p(targets), int(targets.dtype == f32), _p(row_weights), R, C, M, _p(out2),
                                         _p(dpred), _p(ws), self._stream()), "csm_mask_loss")
         return out2, dpred
@@ -1463,22 +1462,22 @@ class HipOps:
             raise ValueError(f"paste_masks: logits must be [N, C, M, M], got {tuple(logits.shape)}")
         N, C, M, _ = logits.shape
         img_h, img_w = int(img_h), int(img_w)
-        self._loss_dense(logits, torch.float32, (N, C, M, M), "paste_masks: logits")
+        self._dense(logits, torch.float32, (N, C, M, M), "paste_masks: logits")
         if labels is not None:
-            self._loss_dense(labels, torch.int32, (N,), "paste_masks: labels")
-        self._loss_dense(boxes, torch.float32, (N, 4), "paste_masks: boxes")
+            self._dense(labels, torch.int32, (N,), "paste_masks: labels")
+        self._dense(boxes, torch.float32, (N, 4), "paste_masks: boxes")
         if out is None:
             out = torch.empty(N, img_h, img_w, dtype=torch.uint8, device=logits.device)
-        self._loss_dense(out, torch.uint8, (N, img_h, img_w), "paste_masks: out")
+        self._dense(out, torch.uint8, (N, img_h, img_w), "paste_masks: out")
         if soft is not None:
-            self._loss_dense(soft, torch.float32, (N, img_h, img_w), "paste_masks: soft")
+            self._dense(soft, torch.float32, (N, img_h, img_w), "paste_masks: soft")
         self._ok(self.lib.csm_paste_masks(_p(logits), _p(labels), _p(boxes), N, C, M, img_h, img_w, float(thr), _p(out), _p(soft),
                                           self._stream()), "csm_paste_masks")
         return out
 
     # -- detector RoI extractor (include/clipself_roi.h) -------------------------------------------------
     def roi_extract_workspace(self, K) -> int:
-        return int(self.lib.csr_roi_extract_workspace(int(K)))
+        return self._size("csr_roi_extract_workspace", int(K))
 
     def _roi_levels(self, maps, grids, scales, B):
         """maps[l]: the level's channel-last map as a 2-D view [B * h_l * w_l, C] (row = one cell, last stride 1, its own row stride);
@@ -1489,51 +1488,32 @@ class HipOps:
         C = maps[0].shape[1]
         arr = (RoiLevel * L)()
         for l, (m, (h, w), s) in enumerate(zip(maps, grids, scales)):
-            if m.dtype != torch.float32 or m.dim() != 2:
-                raise ValueError(f"roi_extract: level {l} must be a 2-D fp32 view [B * h * w, C], got {m.dtype} {tuple(m.shape)}")
-            if tuple(m.shape) != (B * int(h) * int(w), C) or (m.shape[0] > 0 and m.stride(1) != 1):
-                raise ValueError(f"roi_extract: level {l} is {tuple(m.shape)} with strides {m.stride()}, expected [{B} * {h} * {w}, {C}] with last stride 1")
-            ld = m.stride(0) if m.shape[0] > 1 else max(m.stride(0), C)
+            ld = self._rows(m, _F32, B * int(h) * int(w), C, f"roi_extract: level {l}")
             arr[l] = RoiLevel(m.data_ptr(), ld, int(h), int(w), float(s))      # 1.0 / stride in double; the c_float field rounds it once
         return arr, L, C
-
-    @staticmethod
-    def _roi_rows(t, K, P, C, who):
-        if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (K * P * P, C) or (t.shape[0] > 0 and t.stride(1) != 1):
-            raise ValueError(f"roi_extract: {who} must be a 2-D fp32 view [K * P * P, C] = [{K * P * P}, {C}] with last stride 1, "
-                             f"got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
-        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), C)
 
     def roi_extract_fwd(self, maps, grids, scales, rois, out, B, P, sampling_ratio=0, finest_scale=56.0):
         """Multi-level RoIAlign (csr_roi_extract_fwd): rois [K, 5] fp32 (image, x0, y0, x1, y1) -> out, the [K, P, P, C] bins as a 2-D
         view [K * P * P, C].  maps / grids / scales: see _roi_levels; scales[l] = (float)(1 / stride_l)."""
         self._chk(rois, out, *maps)
         K = rois.shape[0]
-        if rois.dtype != torch.float32 or tuple(rois.shape) != (K, 5) or not rois.is_contiguous():
-            raise ValueError(f"roi_extract: rois must be contiguous fp32 [K, 5], got {rois.dtype} {tuple(rois.shape)}")
+        self._dense(rois, torch.float32, (K, 5), "roi_extract: rois")
         arr, L, C = self._roi_levels(maps, grids, scales, B)
-        ldo = self._roi_rows(out, K, P, C, "out")
+        ldo = self._rows(out, _F32, K * P * P, C, "roi_extract: out")
         self._ok(self.lib.csr_roi_extract_fwd(arr, L, int(B), C, _p(rois), K, int(P), int(sampling_ratio), float(finest_scale), _p(out), ldo,
                                               self._stream()), "csr_roi_extract_fwd")
         return out
 
     def roi_extract_bwd(self, dout, rois, dmaps, grids, scales, B, P, sampling_ratio=0, finest_scale=56.0, workspace=None):
         """dmaps[l] += the gradient of roi_extract_fwd's out with respect to level l, all levels in one call (csr_roi_extract_bwd): a
-        gather in ascending box row, no floating-point atomics, equal bits from equal inputs.  The workspace is cached per K (pass
-        workspace= to own it); calls that share a K must share a stream."""
+        gather in ascending box row, no floating-point atomics, equal bits from equal inputs.  The workspace is this header's one
+        buffer per device (pass workspace= to own it); calls that share it must share a stream."""
         self._chk(rois, dout, workspace, *dmaps)
         K = rois.shape[0]
-        if rois.dtype != torch.float32 or tuple(rois.shape) != (K, 5) or not rois.is_contiguous():
-            raise ValueError(f"roi_extract: rois must be contiguous fp32 [K, 5], got {rois.dtype} {tuple(rois.shape)}")
+        self._dense(rois, torch.float32, (K, 5), "roi_extract: rois")
         arr, L, C = self._roi_levels(dmaps, grids, scales, B)
-        ldo = self._roi_rows(dout, K, P, C, "dout")
-        if workspace is None:
-            need = self.roi_extract_workspace(K)
-            cache = self.__dict__.setdefault("_roi_ws", {})
-            key = (K, rois.device)
-            workspace = cache.get(key)
-            if workspace is None and need > 0:
-                workspace = cache[key] = torch.empty(need, dtype=torch.uint8, device=rois.device)
+        ldo = self._rows(dout, _F32, K * P * P, C, "roi_extract: dout")
+        workspace = self._workspace("clipself_roi.h", self.roi_extract_workspace(K), rois.device, workspace, "roi_extract_bwd")
         self._ok(self.lib.csr_roi_extract_bwd(_p(dout), ldo, _p(rois), K, int(P), int(sampling_ratio), float(finest_scale), arr, L, int(B), C,
                                               _p(workspace), self._stream()), "csr_roi_extract_bwd")
         return dmaps

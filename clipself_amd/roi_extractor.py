@@ -20,10 +20,7 @@ import torch
 from torch import nn
 
 from .det_backend import kernel_ops
-
-KERNEL_MAX_LEVELS = 4           # include/clipself_roi.h
-KERNEL_MAX_OUTPUT = 14
-KERNEL_MAX_SAMPLING = 8
+from .hip import ROI_MAX_LEVELS as KERNEL_MAX_LEVELS, ROI_MAX_P as KERNEL_MAX_OUTPUT, ROI_MAX_SR as KERNEL_MAX_SAMPLING  # include/clipself_roi.h
 
 
 def _kernel_ops(t, ops=None):

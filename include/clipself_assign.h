@@ -78,6 +78,10 @@ extern "C" {
 typedef struct ihipStream_t* cs_stream_t; /* == hipStream_t; the same typedef as the other headers, which may be included before this one */
 #endif
 
+#define CSA_MAX_ROWS (1 << 20) /* Nmax */
+#define CSA_MAX_GT 1024        /* Gmax */
+#define CSA_MAX_NUM 4096       /* num */
+
 size_t csa_workspace(int B, int Nmax, int Gmax, int num);
 
 int csa_assign(const float* boxes, long ldb, const int* starts, int K, const float* gt_boxes, long ldg, const int* gt_starts, int Gtot,

@@ -47,6 +47,9 @@ extern "C" {
 typedef struct ihipStream_t* cs_stream_t; /* == hipStream_t; the same typedef as clipself_hip.h, which may be included before this header */
 #endif
 
+#define CSD_MAX_BOXES 16384 /* Kmax */
+#define CSD_MAX_NUM 4096    /* max_num */
+
 size_t csd_nms_workspace(int B, int Kmax, int C_or_G, int max_num);
 
 int csd_nms(const float* boxes, long ldb, const float* scores, long lds, int C, const int* starts, const int* group, int G, int K, int B,

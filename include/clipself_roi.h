@@ -59,6 +59,11 @@ extern "C" {
 typedef struct ihipStream_t* cs_stream_t; /* == hipStream_t; the same typedef as clipself_hip.h / clipself_det.h, which may be included before this header */
 #endif
 
+#define CSR_MAX_LEVELS 4
+#define CSR_MAX_SIDE 512
+#define CSR_MAX_P 14
+#define CSR_MAX_SR 8 /* sampling_ratio */
+
 typedef struct csr_level {
     float* map;          /* forward: the level's map, only read.  backward: the level's gradient map, accumulated into */
     long ld;             /* floats between consecutive cells, >= C */

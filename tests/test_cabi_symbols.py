@@ -1,34 +1,164 @@
-"""CPU: the C-ABI shared library loads and exports every symbol declared in include/clipself_hip.h
-(no compute calls -- there is no GPU in the build container)."""
+"""CPU: the C ABI as one contract.  clipself_amd.hip.ABI maps every public header under include/ to its table of ctypes signatures;
+for each header the names, the arities, the exports of the built library, the includes and plain C99 are held against the header's text,
+the ctypes structs against the C compiler's sizeof / offsetof, and the Python constants against the headers' macros (no compute calls --
+there is no GPU in the build container)."""
+import ctypes
 import re
+import shutil
+import subprocess
 from pathlib import Path
 
 import pytest
 
+from clipself_amd import hip
+
 ROOT = Path(__file__).resolve().parent.parent
+INC = ROOT / "include"
+HEADERS = list(hip.ABI)
+INCLUDES = {"clipself_hip.h": ["<stddef.h>", "<stdint.h>"]}                    # every other header: <stddef.h> alone
+# header -> (HipOps' capability flag, its tensor-level wrappers, the entry points the detector features were merged with)
+DETECTOR = {
+    "clipself_det.h": ("DET_POST", ["nms", "delta2bbox", "nms_workspace"], ["csd_delta2bbox", "csd_nms", "csd_nms_workspace"]),
+    "clipself_roi.h": ("ROI_EXTRACT", ["roi_extract_fwd", "roi_extract_bwd", "roi_extract_workspace"],
+                       ["csr_roi_extract_bwd", "csr_roi_extract_fwd", "csr_roi_extract_workspace"]),
+    "clipself_assign.h": ("ASSIGN", ["assign", "sample", "bbox_targets", "assign_workspace"], ["csa_assign", "csa_sample", "csa_targets", "csa_workspace"]),
+    "clipself_loss.h": ("LOSS", ["rpn_loss", "bbox_head_loss", "loss_workspace"], ["csl_bbox_head_loss", "csl_rpn_loss", "csl_workspace"]),
+    "clipself_mask.h": ("MASK", ["mask_target", "mask_loss", "paste_masks", "mask_workspace"],
+                        ["csm_mask_loss", "csm_mask_target", "csm_paste_masks", "csm_workspace"]),
+    "clipself_rpn.h": ("RPN", ["rpn_select", "rpn_select_workspace"], ["csp_select", "csp_workspace"]),
+    "clipself_conv.h": ("CONV3X3", ["conv3x3", "im2col3x3"], ["csc_conv3x3", "csc_im2col3x3"]),
+    "clipself_bn.h": ("BATCHNORM", ["bn_stats", "bn_finalize", "bn_apply", "bn_bwd_reduce", "bn_bwd_apply", "bn_workspace"],
+                      ["csb_apply", "csb_bwd_apply", "csb_bwd_reduce", "csb_finalize", "csb_row_parts", "csb_stats", "csb_workspace"]),
+}
 
 
-def _declared():
-    text = (ROOT / "include" / "clipself_hip.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(cs_[a-z0-9_]+)\s*\(", text)))
+def _text(header):
+    return re.sub(r"/\*.*?\*/", "", (INC / header).read_text(), flags=re.S)
 
 
-def test_library_exports_every_declared_symbol():
-    from clipself_amd import hip
+def _prefix(header):
+    return next(iter(hip.ABI[header])).split("_")[0] + "_"
+
+
+def _prototypes(header):
+    """name -> argument count of every prototype the header declares."""
+    found = re.findall(r"\b(" + _prefix(header) + r"[a-z0-9_]+)\s*\(([^)]*)\)", _text(header))
+    return {n: len([a for a in args.split(",") if a.strip() not in ("", "void")]) for n, args in found}
+
+
+def _gcc(tmp_path, name, text, *flags):
+    if shutil.which("gcc") is None:
+        pytest.skip("no gcc")
+    src = tmp_path / name
+    src.write_text(text)
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{INC}", str(src), *flags], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+def _run_c(tmp_path, name, body):
+    """The output lines of a C program that includes all the headers."""
+    exe = tmp_path / (name + ".bin")
+    _gcc(tmp_path, name + ".c", "".join(f'#include "{h}"\n' for h in HEADERS) + "#include <stddef.h>\n#include <stdio.h>\nint main(void) {\n"
+         + body + "    return 0;\n}\n", "-o", str(exe))
+    return subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
+
+
+def _library():
     if not hip.library_path().exists():
         hip.build_library()
-    lib = hip.load_library()
-    names = _declared()
-    assert len(names) >= 20
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/clipself_hip.h but not exported"
-    assert sorted(hip.SIGNATURES) == names, "hip.SIGNATURES and the header disagree"
+    return hip.load_library()
+
+
+def test_the_registry_lists_every_public_header():
+    assert sorted(HEADERS) == sorted(p.name for p in INC.glob("*.h")) and len(HEADERS) == 9
+    assert hip.ABI["clipself_hip.h"] is hip.SIGNATURES and len(hip.SIGNATURES) >= 20
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_header_contract(header, tmp_path):
+    table, text, prefix = hip.ABI[header], _text(header), _prefix(header)
+    protos = _prototypes(header)
+    # names: the header's are the table's, and the library exports every one
+    assert sorted(protos) == sorted(table), f"hip.ABI[{header!r}] and the header disagree"
+    assert all(n.startswith(prefix) for n in table)
+    lib = _library()
+    for n in table:
+        assert hasattr(lib, n), f"{n} declared in include/{header} but not exported"
+    # arities: every prototype against its argtypes
+    for n, (_, argtypes) in table.items():
+        assert protos[n] == len(argtypes), n
+    # the prefix belongs to this header alone: no other header declares or mentions it, no other table lists it
+    for other in HEADERS:
+        if other == header:
+            continue
+        assert not any(k.startswith(prefix) for k in hip.ABI[other]), (header, other)
+        if prefix == "cs_":                                                   # cs_stream_t is every header's; entry points are not
+            assert re.findall(r"\bcs_[a-z0-9_]+\s*\(", _text(other)) == [], (header, other)
+        else:
+            assert prefix not in _text(other), (header, other)
+    assert re.findall(r"#\s*include\s*([<\"][^>\"]+[>\"])", text) == INCLUDES.get(header, ["<stddef.h>"])
+    # every source file that defines one of these entry points is compiled against this header
+    csrc = ROOT / "clipself_amd" / "csrc"
+    defined = {}
+    for src in list(csrc.glob("*.hip")) + list(csrc.glob("*.cpp")):
+        for n in re.findall(r'^extern "C" [^(]*?\b(' + prefix + r'[a-z0-9_]+)\s*\(', src.read_text(), flags=re.M):
+            assert f'#include "../../include/{header}"' in src.read_text(), f"{src.name} defines {n} without including {header}"
+            defined[n] = src.name
+    assert sorted(defined) == sorted(table)
+    assert all(Path(src).stem in (csrc / "build.sh").read_text() for src in defined.values())
+    # plain C99: alone, after the headers that came before it, and after all the other eight
+    _gcc(tmp_path, "alone.c", f'#include "{header}"\nint main(void) {{ cs_stream_t s = 0; return s != 0; }}\n', "-pedantic", "-fsyntax-only")
+    before = HEADERS[:HEADERS.index(header)]
+    _gcc(tmp_path, "before.c", "".join(f'#include "{h}"\n' for h in before + [header]), "-pedantic", "-fsyntax-only")
+    _gcc(tmp_path, "last.c", "".join(f'#include "{h}"\n' for h in HEADERS if h != header) + f'#include "{header}"\n', "-fsyntax-only")
+    # the tensor-level face
+    if header in DETECTOR:
+        flag, wrappers, names = DETECTOR[header]
+        assert getattr(hip.HipOps, flag) is True and sorted(table) == names
+        for m in wrappers:
+            assert callable(getattr(hip.HipOps, m)), m
+    if header == "clipself_conv.h":
+        from _conv_ref import RefOpsConv
+        assert all(callable(getattr(RefOpsConv, n[len(prefix):])) for n in table)
+
+
+def test_header_is_plain_c_and_links_against_the_library(tmp_path):
+    """The headers are the binding contract for non-C++ hosts: a C program that includes all nine and takes the address of every declared
+    entry point must link against libclipself_hip.so (no call is made -- there is no GPU here)."""
+    _library()
+    names = [n for h in HEADERS for n in hip.ABI[h]]
+    lib = hip.library_path()
+    _gcc(tmp_path, "bind.c", "".join(f'#include "{h}"\n' for h in HEADERS) + "#include <stdio.h>\nint main(void) {\n    const void* table[] = {\n"
+         + "".join(f"        (const void*){n},\n" for n in names)
+         + '    };\n    printf("%d\\n", (int)(sizeof table / sizeof table[0]));\n    return 0;\n}\n',
+         "-o", str(tmp_path / "bind"), f"-L{lib.parent}", "-l:" + lib.name, f"-Wl,-rpath,{lib.parent}", "-Wl,--unresolved-symbols=ignore-in-shared-libs")
+
+
+def test_ctypes_structs_have_the_c_layout(tmp_path):
+    """sizeof and every field's offsetof, as the C compiler sees the headers' structs, equal the ctypes classes'; the field names are the
+    header's, in its order."""
+    assert sorted(hip.STRUCTS) == sorted(re.findall(r"typedef struct (\w+) \{", "".join(_text(h) for h in HEADERS)))
+    body, want = "", []
+    for name, cls in hip.STRUCTS.items():
+        fields = [f for f, _ in cls._fields_]
+        decl = re.search(r"typedef struct " + name + r" \{(.*?)\}", "".join(_text(h) for h in HEADERS), flags=re.S).group(1)
+        assert [f.strip().split()[-1].lstrip("*") for f in decl.replace(", ", ";").split(";") if f.strip()] == fields, name
+        body += f'    printf("%d\\n", (int)sizeof({name}));\n' + "".join(f'    printf("%d\\n", (int)offsetof({name}, {f}));\n' for f in fields)
+        want += [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert [int(v) for v in _run_c(tmp_path, "structs", body)] == want
+
+
+def test_python_constants_are_the_headers_macros(tmp_path):
+    """Every limit and layout constant of the headers (CS?_MAX_*, *_EXTRA, CS_ADAMW_GUARD_*) is registered in hip.MACROS, and its value as
+    the C compiler evaluates it is the Python constant."""
+    in_headers = set(re.findall(r"^#define (CS[A-Z]?_(?:MAX_\w+|\w+_EXTRA|ADAMW_GUARD_\w+))\b", "".join(_text(h) for h in HEADERS), flags=re.M))
+    assert in_headers == set(hip.MACROS)
+    got = _run_c(tmp_path, "macros", "".join(f'    printf("%lld\\n", (long long)({m}));\n' for m in hip.MACROS))
+    assert dict(zip(hip.MACROS, (int(v) for v in got))) == hip.MACROS
 
 
 def test_ops_refuse_to_run_without_gpu():
     import torch
-    from clipself_amd import hip
     if torch.cuda.is_available():
         pytest.skip("GPU present")
     with pytest.raises(RuntimeError):
@@ -50,28 +180,6 @@ def test_every_entry_point_has_a_tensor_level_wrapper_and_a_reference_op():
         name = renamed.get(sym, sym[len("cs_"):])
         assert callable(getattr(hip.HipOps, name, None)), f"HipOps.{name} missing for {sym}"
         assert callable(getattr(RefOps, name, None)), f"RefOps.{name} missing for {sym}"
-
-
-def test_header_is_plain_c_and_links_against_the_library(tmp_path):
-    """include/clipself_hip.h is the binding contract for non-C++ hosts: it must compile as C99 on its own, and a C program that takes the
-    address of every declared entry point must link against libclipself_hip.so (no call is made -- there is no GPU here)."""
-    import shutil
-    import subprocess
-    from clipself_amd import hip
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    if not hip.library_path().exists():
-        hip.build_library()
-    names = _declared()
-    src = tmp_path / "bind.c"
-    src.write_text('#include "clipself_hip.h"\n#include <stdio.h>\nint main(void) {\n    const void* table[] = {\n'
-                   + "".join(f"        (const void*){n},\n" for n in names)
-                   + '    };\n    printf("%d\\n", (int)(sizeof table / sizeof table[0]));\n    return 0;\n}\n')
-    lib = hip.library_path()
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(src), "-o", str(tmp_path / "bind"),
-                        f"-L{lib.parent}", "-l:" + lib.name, f"-Wl,-rpath,{lib.parent}", "-Wl,--unresolved-symbols=ignore-in-shared-libs"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 def test_compute_unit_reservations_compose():

@@ -7,8 +7,6 @@ bounds reject four planted errors.  The mmdet-named modules built from the refer
 import ctypes
 import json
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -340,59 +338,6 @@ def test_no_host_reads_on_the_kernel_route():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "clipself_loss.h").read_text(), flags=re.S)
-    return text, sorted(set(re.findall(r"\b(csl_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_header_names_signatures_and_the_other_abis_stay_apart():
-    from clipself_amd import hip
-    text, names = _declared()
-    assert names == ["csl_bbox_head_loss", "csl_rpn_loss", "csl_workspace"]
-    assert names == sorted(hip.LOSS_SIGNATURES)
-    assert not set(hip.LOSS_SIGNATURES) & (set(hip.SIGNATURES) | set(hip.DET_SIGNATURES) | set(hip.ROI_SIGNATURES) | set(hip.ASSIGN_SIGNATURES))
-    assert re.findall(r"\b(cs_[a-z0-9_]+)\s*\(", text) == [] and "csd_" not in text and "csr_" not in text and "csa_" not in text
-    assert re.findall(r"#\s*include\s*([<\"][^>\"]+[>\"])", text) == ["<stddef.h>"]
-    for other in ("clipself_hip.h", "clipself_det.h", "clipself_roi.h", "clipself_assign.h"):
-        assert "csl_" not in re.sub(r"/\*.*?\*/", "", (ROOT / "include" / other).read_text(), flags=re.S)
-    for name in names:
-        proto = re.search(name + r"\s*\(([^)]*)\)", text).group(1)
-        assert len(proto.split(",")) == len(hip.LOSS_SIGNATURES[name][1]), name
-    fields = re.search(r"typedef struct csl_level \{(.*?)\}", text, flags=re.S).group(1)
-    assert [f.strip().split()[-1].lstrip("*") for f in fields.replace(", ", ";").split(";") if f.strip()] == [n for n, _ in hip.LossLevel._fields_]
-    assert hip.HipOps.LOSS is True
-    for m in ("rpn_loss", "bbox_head_loss", "loss_workspace"):
-        assert callable(getattr(hip.HipOps, m))
-    assert "det_loss" in (ROOT / "clipself_amd" / "csrc" / "build.sh").read_text()
-
-
-def test_header_is_plain_c99_and_its_symbols_link(tmp_path):
-    from clipself_amd import hip
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    if not hip.library_path().exists():
-        hip.build_library()
-    lib = hip.load_library()
-    _, names = _declared()
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/clipself_loss.h but not exported"
-    alone = tmp_path / "alone.c"
-    alone.write_text('#include "clipself_loss.h"\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", f"-I{ROOT / 'include'}", "-c", str(alone), "-o", str(tmp_path / "alone.o")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    src = tmp_path / "bind.c"                                               # all five headers together
-    src.write_text('#include "clipself_hip.h"\n#include "clipself_det.h"\n#include "clipself_roi.h"\n#include "clipself_assign.h"\n'
-                   '#include "clipself_loss.h"\n#include <stdio.h>\n'
-                   'int main(void) {\n    const void* table[] = {\n' + "".join(f"        (const void*){n},\n" for n in names)
-                   + '    };\n    printf("%d\\n", (int)(sizeof table / sizeof table[0]));\n    return 0;\n}\n')
-    p = hip.library_path()
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(src), "-o", str(tmp_path / "bind"),
-                        f"-L{p.parent}", "-l:" + p.name, f"-Wl,-rpath,{p.parent}", "-Wl,--unresolved-symbols=ignore-in-shared-libs"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
 def test_limits_are_refused_without_a_device():
     """Argument checks come before any launch, so the -1 cases can be seen here: no pointer is touched."""
     from clipself_amd import hip

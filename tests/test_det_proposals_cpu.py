@@ -2,15 +2,10 @@
 
 The torch route (`select_torch`, `rpn_proposals` on CPU tensors) against the numpy restatement (tests/_proposal_ref.py) on every case of the
 GPU list: exact anchor indices, starts and decided groups, scores and boxes inside their derived bounds, end-to-end proposals bit-equal;
-the header as plain C99, its symbols in the library and in hip.RPN_SIGNATURES with matching arities; every -1 case of the header through
-the raw entry point (argument checks come before any launch); cfg validation; `rcnn_targets(proposal_counts=)`; the conditions the GPU
+every -1 case of the header through the raw entry point (the header itself is held by tests/test_cabi_symbols.py) (argument checks come before any launch); cfg validation; `rcnn_targets(proposal_counts=)`; the conditions the GPU
 tests rely on, asserted from the restatement alone (no row in the min-size band, score gaps of the end-to-end cases above four bounds);
 and the bounds rejecting six planted errors."""
 import ctypes
-import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -18,7 +13,6 @@ import torch
 
 import _proposal_ref as P
 
-ROOT = Path(__file__).resolve().parent.parent
 ALL = list(P.SELECT_CASES) + list(P.E2E_CASES)
 
 
@@ -84,61 +78,6 @@ def test_get_bboxes_returns_mmdets_lists_and_takes_an_anchor_generator():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _header():
-    return re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "clipself_rpn.h").read_text(), flags=re.S)
-
-
-def _declared():
-    return sorted(set(re.findall(r"\b(csp_[a-z0-9_]+)\s*\(", _header())))
-
-
-def test_header_names_signatures_and_the_other_tables_stay_apart():
-    from clipself_amd import hip
-    names = _declared()
-    assert names == ["csp_select", "csp_workspace"]
-    assert sorted(hip.RPN_SIGNATURES) == names
-    others = (hip.SIGNATURES, hip.DET_SIGNATURES, hip.ROI_SIGNATURES, hip.ASSIGN_SIGNATURES, hip.LOSS_SIGNATURES, hip.MASK_SIGNATURES)
-    for t in others:
-        assert not set(hip.RPN_SIGNATURES) & set(t)
-    text = _header()
-    assert re.findall(r"\b(cs_[a-z0-9_]+)\s*\(", text) == []                # nothing of the engine's ABI (the regex of test_cabi_symbols.py)
-    assert re.findall(r"#\s*include\s*([<\"][^>\"]+[>\"])", text) == ["<stddef.h>"]
-    for n in names:                                                        # prototype arities
-        proto = re.search(r"\b" + n + r"\s*\(([^)]*)\)", text).group(1)
-        assert len([a for a in proto.split(",") if a.strip()]) == len(hip.RPN_SIGNATURES[n][1]), n
-    assert ctypes.sizeof(hip.RpnLevel) == 2 * ctypes.sizeof(ctypes.c_void_p) + 2 * ctypes.sizeof(ctypes.c_int)
-    assert hip.HipOps.RPN is True and callable(hip.HipOps.rpn_select) and callable(hip.HipOps.rpn_select_workspace)
-    for h in ("clipself_hip.h", "clipself_det.h", "clipself_roi.h", "clipself_assign.h", "clipself_loss.h", "clipself_mask.h"):
-        assert "csp_" not in re.sub(r"/\*.*?\*/", "", (ROOT / "include" / h).read_text(), flags=re.S)
-
-
-def test_header_is_plain_c99_and_its_symbols_link(tmp_path):
-    from clipself_amd import hip
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    if not hip.library_path().exists():
-        hip.build_library()
-    lib = hip.load_library()
-    names = _declared()
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/clipself_rpn.h but not exported"
-    alone = tmp_path / "alone.c"
-    alone.write_text('#include "clipself_rpn.h"\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", f"-I{ROOT / 'include'}", "-c", str(alone), "-o", str(tmp_path / "alone.o")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    src = tmp_path / "bind.c"                                               # all seven headers together, this one last
-    src.write_text("".join(f'#include "clipself_{h}.h"\n' for h in ("hip", "det", "roi", "assign", "loss", "mask", "rpn"))
-                   + "#include <stdio.h>\nint main(void) {\n    csp_level lv = {0, 0, 1, 1};\n    const void* table[] = {\n"
-                   + "".join(f"        (const void*){n},\n" for n in names)
-                   + '    };\n    printf("%d %d\\n", (int)(sizeof table / sizeof table[0]), lv.h);\n    return 0;\n}\n')
-    p = hip.library_path()
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(src), "-o", str(tmp_path / "bind"),
-                        f"-L{p.parent}", "-l:" + p.name, f"-Wl,-rpath,{p.parent}", "-Wl,--unresolved-symbols=ignore-in-shared-libs"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
 def _levels(hip, dims, cls=1 << 20, reg=1 << 20):
     arr = (hip.RpnLevel * len(dims))()
     for l, (h, w) in enumerate(dims):

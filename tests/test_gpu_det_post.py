@@ -258,3 +258,64 @@ def test_detections_on_the_backbone_fixture(hip):
     want = R.multiclass(boxes.cpu().numpy(), scores[:, :C1 - 1].cpu().numpy(), starts, 32, 0.02, 0.5, 20)
     assert int(want[3].min()) > 0
     R.compare("fixture", [t.cpu().numpy() for t in (dets, labels, inds, counts)], want)
+
+
+# ------------------------------------------------------------------------------------------------ the shared workspace of HipOps
+def _boxes(g, n, side=64.0):
+    xy = torch.rand(n, 2, generator=g) * (side - 24)
+    return torch.cat([xy, xy + 2 + torch.rand(n, 2, generator=g) * 20], 1)
+
+
+def test_one_workspace_per_header_serves_small_large_small():
+    """HipOps keeps one grow-only workspace per header and device.  A small call, a large one and the small one again, on one stream,
+    each give the bits of the same call with a fresh workspace of exactly the size the library asks for: a grown buffer carries nothing
+    into a smaller call, and a small buffer is never handed to a larger one.  Afterwards there is one buffer per header, not per shape."""
+    from clipself_amd.hip import HipOps
+    ops = HipOps()                                                 # its own caches: the count at the end is exact
+    g = torch.Generator().manual_seed(11)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    fresh = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
+
+    def same(a, b, what):
+        torch.cuda.synchronize()
+        for x, y in zip(a, b):
+            assert torch.equal(x.view(torch.uint8), y.view(torch.uint8)), what
+
+    largest = {}
+
+    def nms(B, Kmax):
+        boxes, scores = _boxes(g, B * Kmax).cuda(), torch.rand(B * Kmax, 2, generator=g).cuda()
+        starts = (torch.arange(B + 1, dtype=torch.int32) * Kmax).cuda()
+        need = ops.nms_workspace(B, Kmax, 2, 10)
+        largest["clipself_det.h"] = max(largest.get("clipself_det.h", 0), need)
+        same(ops.nms(boxes, scores, starts, Kmax, 0.05, 0.5, 10), ops.nms(boxes, scores, starts, Kmax, 0.05, 0.5, 10, workspace=fresh(need)),
+             f"nms B = {B}, Kmax = {Kmax}")
+
+    def assign(Nmax, Gmax=3):
+        boxes, gts = _boxes(g, Nmax).cuda(), _boxes(g, Gmax).cuda()
+        gs = torch.tensor([0, Gmax], dtype=torch.int32, device=dev)
+        need = ops.assign_workspace(1, Nmax, Gmax)
+        largest["clipself_assign.h"] = max(largest.get("clipself_assign.h", 0), need)
+        same(ops.assign(boxes, None, gts, gs, 1, Nmax, Gmax, 0.5, 0.4, 0.1), ops.assign(boxes, None, gts, gs, 1, Nmax, Gmax, 0.5, 0.4, 0.1, workspace=fresh(need)),
+             f"assign Nmax = {Nmax}")
+
+    def roi_bwd(K, P=2, C=8):
+        grids, scales = [(4, 4), (2, 2)], [0.25, 0.125]           # a 16 x 16 image at strides 4 and 8; boxes of both levels
+        half = torch.where(torch.arange(K) % 2 == 0, 1.5, 5.0)[:, None]
+        ctr = 6 + torch.rand(K, 2, generator=g) * 4
+        rois = torch.cat([torch.zeros(K, 1), ctr - half, ctr + half], 1).cuda()
+        dout = torch.randn(K * P * P, C, generator=g).cuda()
+        need = ops.roi_extract_workspace(K)
+        largest["clipself_roi.h"] = max(largest.get("clipself_roi.h", 0), need)
+        run = lambda **kw: ops.roi_extract_bwd(dout, rois, [torch.zeros(h * w, C, device=dev) for h, w in grids], grids, scales, 1, P, 0, 4.0, **kw)
+        a, b = run(), run(workspace=fresh(need))
+        same(a, b, f"roi_extract_bwd K = {K}")
+        assert all(bool(t.abs().sum() > 0) for t in a), "both levels must receive gradient"
+
+    for B, Kmax in ((1, 8), (2, 300), (1, 8)):
+        nms(B, Kmax)
+    for Nmax in (16, 600, 16):
+        assign(Nmax)
+    for K in (3, 70, 3):
+        roi_bwd(K)
+    assert {k: v.numel() for k, v in ops._ws.items()} == {(h, dev): n for h, n in largest.items()}

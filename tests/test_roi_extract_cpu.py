@@ -2,12 +2,8 @@
 
 Known answers of the contract by hand; the two forms of the numpy restatement (tests/_roi_extract_ref.py) against each other; the torch
 route, forward and autograd backward, against the restatement on the GPU file's case list -- bit for bit on the lattice cases, inside the
-derived bound on the random ones; the reference's two extractor dicts and the unsupported options; the header as plain C99 and its
-symbols in the library and in hip.ROI_SIGNATURES."""
-import re
-import shutil
-import subprocess
-from pathlib import Path
+derived bound on the random ones; the reference's two extractor dicts and the unsupported options; every -1 case of the header through
+the raw entry points (the header itself is held by tests/test_cabi_symbols.py)."""
 
 import numpy as np
 import pytest
@@ -15,7 +11,6 @@ import torch
 
 import _roi_extract_ref as R
 
-ROOT = Path(__file__).resolve().parent.parent
 NAN, INF = float("nan"), float("inf")
 STRIDES = [4, 8, 16, 32]
 
@@ -187,63 +182,6 @@ def test_hostile_boxes_pool_to_zero_on_the_torch_route():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def _declared():
-    text = (ROOT / "include" / "clipself_roi.h").read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return text, sorted(set(re.findall(r"\b(csr_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_header_names_signatures_and_the_other_abis_stay_apart():
-    from clipself_amd import hip
-    text, names = _declared()
-    assert names == ["csr_roi_extract_bwd", "csr_roi_extract_fwd", "csr_roi_extract_workspace"]
-    assert names == sorted(hip.ROI_SIGNATURES)
-    assert not set(hip.ROI_SIGNATURES) & (set(hip.SIGNATURES) | set(hip.DET_SIGNATURES))
-    cs = re.compile(r"\b(cs_[a-z0-9_]+)\s*\(")                                # the regex of test_cabi_symbols.py
-    assert cs.findall(text) == [] and "csd_" not in text
-    for other in ("clipself_hip.h", "clipself_det.h"):
-        assert "csr_" not in re.sub(r"/\*.*?\*/", "", (ROOT / "include" / other).read_text(), flags=re.S)
-    assert re.findall(r"#\s*include\s*([<\"][^>\"]+[>\"])", text) == ["<stddef.h>"]
-    assert hip.HipOps.ROI_EXTRACT is True and callable(hip.HipOps.roi_extract_fwd) and callable(hip.HipOps.roi_extract_bwd)
-
-
-def test_header_is_plain_c99_and_its_symbols_link(tmp_path):
-    from clipself_amd import hip
-    if shutil.which("gcc") is None:
-        pytest.skip("no gcc")
-    if not hip.library_path().exists():
-        hip.build_library()
-    lib = hip.load_library()
-    _, names = _declared()
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/clipself_roi.h but not exported"
-    alone = tmp_path / "alone.c"
-    alone.write_text('#include "clipself_roi.h"\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", f"-I{ROOT / 'include'}", "-c", str(alone), "-o", str(tmp_path / "alone.o")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    src = tmp_path / "bind.c"                                               # the three headers together, the engine's first
-    src.write_text('#include "clipself_hip.h"\n#include "clipself_det.h"\n#include "clipself_roi.h"\n#include <stdio.h>\nint main(void) {\n'
-                   '    const void* table[] = {\n' + "".join(f"        (const void*){n},\n" for n in names)
-                   + '    };\n    csr_level lv;\n    lv.h = 1;\n    printf("%d %d\\n", (int)(sizeof table / sizeof table[0]), lv.h);\n    return 0;\n}\n')
-    p = hip.library_path()
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(src), "-o", str(tmp_path / "bind"),
-                        f"-L{p.parent}", "-l:" + p.name, f"-Wl,-rpath,{p.parent}", "-Wl,--unresolved-symbols=ignore-in-shared-libs"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    size = tmp_path / "size.c"                                              # the ctypes mirror of csr_level has the C struct's size
-    size.write_text('#include "clipself_roi.h"\n#include <stdio.h>\nint main(void) { printf("%d\\n", (int)sizeof(csr_level)); return 0; }\n')
-    r = subprocess.run(["gcc", "-std=c99", f"-I{ROOT / 'include'}", str(size), "-o", str(tmp_path / "size")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert int(subprocess.run([str(tmp_path / "size")], capture_output=True, text=True).stdout) == ctypes_sizeof_level() == 32
-
-
-def ctypes_sizeof_level():
-    import ctypes
-    from clipself_amd import hip
-    return ctypes.sizeof(hip.RoiLevel)
-
-
 def test_limits_are_refused_without_a_device():
     """Argument checks come before any launch, so the -1 cases can be seen here: no pointer is touched."""
     from clipself_amd import hip
