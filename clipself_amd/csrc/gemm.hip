@@ -141,6 +141,7 @@ template <int ACT>
 __device__ __forceinline__ float activate(float v) {
     if (ACT == 1) return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));                       // nn.GELU (open_clip/transformer.py:195,211)
     if (ACT == 2) return v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * v));   // QuickGELU (:31-34)
+    if (ACT == 3) return v < 0.f ? 0.f : v;                    // ReLU (F-ViT/models/fvit_head.py:83): a NaN passes, as through torch's
     return v;
 }
 
@@ -693,7 +694,53 @@ int launch(GemmArgs a, int splits, int use_glds, int force_cfg, hipStream_t stre
     }
 }
 
+// ------------------------------------------------------------------------------------------------ split-K behind a bf16 epilogue
+// The skinny, deep GEMMs of the detector's box head (4096 x 512 outputs, K = 12 544: 32 tiles of 256 x 256 on 256 CUs with 196 K tiles
+// behind each): the K tiles are cut into `splits` contiguous slices, slice y writes its fp32 partial [M, N] to ws + y*M*N with plain
+// stores (launch<EPI_F32> with split_stride, the path of cs_gemm_wgrad), and this kernel adds the partials in ascending slice order, adds
+// the bias once, applies the activation and writes the bf16 rows at ldc.  No atomics: the same (M, N, K, splits) gives the same bits.
+// One thread per four columns: 16-byte loads, one 8-byte store; columns >= N of a padded C are never touched (N % 4 == 0).
+__global__ __launch_bounds__(256) void splitk_reduce_act_kernel(const float* __restrict__ ws, int splits, long stride,
+                                                                const float* __restrict__ bias, __bf16* __restrict__ C, int M, int N,
+                                                                int ldc, int relu) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int n4 = N >> 2;
+    if (i >= (long)M * n4) return;
+    const int row = (int)(i / n4), c = (int)(i - (long)row * n4) * 4;
+    const float* src = ws + (size_t)row * N + c;
+    float4 acc = *(const float4*)src;
+    for (int s = 1; s < splits; ++s) {
+        const float4 t = *(const float4*)(src + (size_t)s * stride);
+        acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
+    }
+    if (bias) {
+        const float4 b = *(const float4*)(bias + c);
+        acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
+    }
+    if (relu) { acc.x = activate<3>(acc.x); acc.y = activate<3>(acc.y); acc.z = activate<3>(acc.z); acc.w = activate<3>(acc.w); }
+    union { bf16x2 v; uint32_t u; } lo, hi;
+    lo.v[0] = f2bf(acc.x); lo.v[1] = f2bf(acc.y);
+    hi.v[0] = f2bf(acc.z); hi.v[1] = f2bf(acc.w);
+    *(uint2*)(C + (size_t)row * ldc + c) = make_uint2(lo.u, hi.u);
+}
+
+// The slice count of `splits <= 0` for epilogues 0 and 9: a pure function of M, N, K, the 256 x 256 tile and the CU count, restated by
+// HipOps.gemm_nt_splits (the caller sizes the workspace with it).  Doubled while (a) the slices of all tiles still fit the CUs in one
+// round and (b) each slice keeps at least SPLITK_MIN_KTILES K tiles, up to SPLITK_MAX.  Fixed from the sweep of tools/fc_bench.py
+// (profiles/fc_bench.md, forward, us at 1 / 2 / 4 / 8 slices): 4096 x 512 x 12544: 177 / 102 / 77 / 70 -> 8; 8000 x 512 x 12544:
+// 183 / 114 / 114 / 140 -> 4; 4096 x 768 x 12544: 179 / 106 / 96 / 121 -> 4; 4096 x 512 x 512: 24 / 27 / 27 / 30 -> 1 (eight K tiles).
+constexpr int SPLITK_MAX = 8, SPLITK_MIN_KTILES = 16;
+int choose_bf16_splits(int M, int N, int K) {
+    const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
+    const int ktiles = K / BK;
+    int s = 1;
+    while (s < SPLITK_MAX && tiles * (s * 2) <= cs_num_cus() && ktiles / (s * 2) >= SPLITK_MIN_KTILES) s *= 2;
+    return s;
+}
+
 }  // namespace
+
+static int gemm_nt_split_f32(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int cfg, int splits, hipStream_t stream);
 
 // C ABI ------------------------------------------------------------------------------------------
 // epi: 0 bf16 out (+bias) | 1 f32 out (+bias) | 2 f32 out = extra(residual) + acc + bias |
@@ -701,6 +748,9 @@ int launch(GemmArgs a, int splits, int use_glds, int force_cfg, hipStream_t stre
 //      4 f32 atomic accumulate (split-K, C pre-zeroed or accumulating) |
 //      5 patch-embed: out row = row + row/group + 1, += extra[(row%group+1)*ldc + col] |
 //      6 residual with a folded LayerNorm (cs_gemm_nt_ln) | 7 bf16 out = GELU(acc + bias) (exact, erf) | 8 bf16 out = QuickGELU(acc + bias)
+//      9 bf16 out = ReLU(acc + bias)
+// splits: 1, except epilogue 4 (atomic) and epilogues 0 / 9 without a folded LayerNorm, whose split-K goes through fp32 partials in `extra`
+//      (>= splits*M*N floats) and splitk_reduce_act_kernel; <= 0 = chosen here (choose_bf16_splits).
 // flags bit0: 0 = global_load_lds staging, 1 = register staging (debug/fallback A-B switch)
 //       bits 4-7: force schedule (1 = 128x128, 2 = 256x128, 3 = 256x256 lockstep, 7 = 256x256 split rings A3/B2 (one tile per workgroup),
 //                 9 = persistent split rings (bf16 / GELU / SwiGLU / residual epilogues through LDS slabs),
@@ -722,10 +772,29 @@ static int gemm_nt_impl(const void* A, const void* B, void* C, const float* bias
     CS_CHECK_ARG(K % BK == 0, "cs_gemm_nt: K=%d must be a multiple of %d", K, BK);
     CS_CHECK_ARG((lda % 8) == 0 && (ldb % 8) == 0, "cs_gemm_nt: lda/ldb must be multiples of 8 (16-byte rows)");
     CS_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "cs_gemm_nt: operands must be 16-byte aligned");
-    CS_CHECK_ARG(splits == 1 || epi == EPI_ATOMIC_F32, "cs_gemm_nt: split-K (splits != 1; <= 0 = automatic) needs the atomic epilogue");
+    const bool splitk_bf16 = (epi == EPI_BF16 || epi == EPI_RELU_BF16) && ln_mean == nullptr;
+    CS_CHECK_ARG(splits == 1 || epi == EPI_ATOMIC_F32 || splitk_bf16,
+                 "cs_gemm_nt: split-K (splits != 1; <= 0 = automatic) exists for epilogues 0 and 9 (through a workspace) and 4 (atomic), not %d", epi);
     CS_CHECK_ARG((epi == EPI_SWIGLU_BF16 ? group : N) % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C % 16) == 0,
                  "cs_gemm_nt: N, ldc must be multiples of 4 and C 16-byte aligned (vector epilogue)");
     CS_CHECK_ARG(bias == nullptr || ((uintptr_t)bias % 16) == 0, "cs_gemm_nt: bias must be 16-byte aligned");
+    if (splitk_bf16 && splits != 1) {                      // deterministic split-K: fp32 partials in `extra`, then splitk_reduce_act_kernel
+        const int ns = splits > 0 ? splits : choose_bf16_splits(M, N, K);
+        CS_CHECK_ARG(ns <= K / BK, "cs_gemm_nt: splits=%d exceeds the %d K tiles of K=%d", ns, K / BK, K);
+        if (ns > 1) {
+            CS_CHECK_ARG(extra != nullptr && ((uintptr_t)extra % 16) == 0,
+                         "cs_gemm_nt: split-K of epilogue %d needs `extra` = a 16-byte aligned fp32 workspace of splits*M*N = %ld floats", epi,
+                         (long)ns * M * N);
+            const int rc = gemm_nt_split_f32(A, B, (float*)extra, M, N, K, lda, ldb, (flags >> 4) & 15, ns, stream);
+            if (rc != 0) return rc;
+            const long n = (long)M * (N >> 2);
+            hipLaunchKernelGGL(splitk_reduce_act_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, extra, ns, (long)M * N, bias,
+                               (__bf16*)C, M, N, ldc, epi == EPI_RELU_BF16 ? 1 : 0);
+            CS_LAUNCH_CHECK();
+            return 0;
+        }
+        splits = 1;                                        // one slice: the plain kernel, `extra` unused
+    }
     GemmArgs a;
     a.A = (const __bf16*)A; a.B = (const __bf16*)B; a.C = C; a.bias = bias; a.extra = extra;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.group = group;
@@ -772,6 +841,7 @@ static int gemm_nt_impl(const void* A, const void* B, void* C, const float* bias
         case EPI_RESID_LN_F32: return launch<EPI_RESID_LN_F32>(a, splits, glds, force, stream);
         case EPI_GELU_BF16: return launch<EPI_GELU_BF16>(a, splits, glds, force, stream);
         case EPI_QGELU_BF16: return launch<EPI_QGELU_BF16>(a, splits, glds, force, stream);
+        case EPI_RELU_BF16: return launch<EPI_RELU_BF16>(a, splits, glds, force, stream);
     }
     cs_set_error("cs_gemm_nt: unknown epilogue %d", epi);
     return -1;

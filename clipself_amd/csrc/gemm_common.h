@@ -17,10 +17,11 @@
 
 constexpr int BK = 64;
 enum Epi { EPI_BF16 = 0, EPI_F32 = 1, EPI_RESID_F32 = 2, EPI_SWIGLU_BF16 = 3, EPI_ATOMIC_F32 = 4, EPI_PATCH_F32 = 5, EPI_RESID_LN_F32 = 6,
-           EPI_GELU_BF16 = 7, EPI_QGELU_BF16 = 8 };
-// bf16 output of acc + bias, optionally through the MLP activation of the OpenAI-CLIP ViT (0 none, 1 exact GELU, 2 QuickGELU)
-constexpr bool epi_is_bf16(int e) { return e == EPI_BF16 || e == EPI_GELU_BF16 || e == EPI_QGELU_BF16; }
-constexpr int epi_act(int e) { return e == EPI_GELU_BF16 ? 1 : (e == EPI_QGELU_BF16 ? 2 : 0); }
+           EPI_GELU_BF16 = 7, EPI_QGELU_BF16 = 8, EPI_RELU_BF16 = 9 };
+// bf16 output of acc + bias, optionally through an activation: the MLP's of the OpenAI-CLIP ViT (1 exact GELU, 2 QuickGELU) or the ReLU
+// behind the detector's FCs (3); 0 none
+constexpr bool epi_is_bf16(int e) { return e == EPI_BF16 || e == EPI_GELU_BF16 || e == EPI_QGELU_BF16 || e == EPI_RELU_BF16; }
+constexpr int epi_act(int e) { return e == EPI_GELU_BF16 ? 1 : (e == EPI_QGELU_BF16 ? 2 : (e == EPI_RELU_BF16 ? 3 : 0)); }
 
 struct GemmArgs {
     const __bf16* A;

@@ -18,6 +18,8 @@ _CSRC = Path(__file__).resolve().parent / "csrc"
 _LIB_PATH = Path(os.environ["CLIPSELF_HIP_LIB"]) if os.environ.get("CLIPSELF_HIP_LIB") else _CSRC / "libclipself_hip.so"   # override: A/B of two builds
 
 EPI_BF16, EPI_F32, EPI_RESID_F32, EPI_SWIGLU_BF16, EPI_ATOMIC_F32, EPI_PATCH_F32, EPI_RESID_LN_F32, EPI_GELU_BF16, EPI_QGELU_BF16 = range(9)
+EPI_RELU_BF16 = 9                       # bf16 = ReLU(acc + bias): the detector box head's Linear + ReLU (linear.LinearAct)
+SPLITK_MAX, SPLITK_MIN_KTILES = 8, 16   # cs_gemm_nt's choice of `splits` for epilogues 0 / 9 (include/clipself_hip.h), restated by gemm_nt_splits
 DX_BF16, DX_F32_ASSIGN, DX_F32_ACCUM = range(3)
 ADAMW_GUARD_HEAD, ADAMW_GUARD_SPAN = 8, 16384
 
@@ -271,6 +273,7 @@ class HipOps:
     RPN = True                          # rpn_select: per-level top-k of the RPN maps, decode and min-size filter, the input of nms' group form (det_proposals)
     CONV3X3 = True                      # conv3x3 / im2col3x3: Conv2d(Cin, Cout, 3, padding=1) on channel-last rows as an implicit GEMM (conv.Conv3x3)
     BATCHNORM = True                    # bn_stats / bn_finalize / bn_apply / bn_bwd_reduce / bn_bwd_apply: batch norm (+ ReLU) on channel-last rows (norm_act.BatchNormAct2d)
+    LINEAR_ACT = True                   # gemm_nt(epi=EPI_RELU_BF16, splits=, extra=workspace): Linear + ReLU with deterministic split-K (linear.LinearAct)
     BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -419,8 +422,24 @@ class HipOps:
         assert B.shape[1] == K and A.stride(1) == 1 and B.stride(1) == 1 and C.stride(-1) == 1
         if extra is not None and epi in (EPI_RESID_F32, EPI_PATCH_F32):
             assert extra.stride(0) == C.stride(0), "extra must share C's row stride"
+        if epi in (EPI_BF16, EPI_RELU_BF16) and splits != 1 and extra is not None:
+            # split-K through partials: `extra` is the fp32 workspace.  Its size is checked here (the library sees a pointer); a missing or
+            # misaligned one is the library's to refuse
+            s = splits if splits > 0 else self.gemm_nt_splits(M, N, K)
+            if s > 1 and (extra.dtype != torch.float32 or not extra.is_contiguous() or extra.numel() < s * M * N):
+                raise ValueError(f"gemm_nt: split-K with {s} slices needs a contiguous fp32 workspace of {s} * {M} * {N} = {s * M * N} "
+                                 f"floats in `extra`, got {extra.dtype} with {extra.numel()} elements")
         self._ok(self.lib.cs_gemm_nt(_p(A), _p(B), _p(C), _p(bias), _p(extra), M, N, K, A.stride(0), B.stride(0),
                                      C.stride(0), epi, splits, group, flags | self.gemm_flags, self._stream()), "cs_gemm_nt")
+
+    def gemm_nt_splits(self, M, N, K) -> int:
+        """The slice count cs_gemm_nt chooses for splits <= 0 on epilogues 0 / 9 (the rule of include/clipself_hip.h): what a caller sizes the
+        workspace with.  1 = the plain call, no workspace."""
+        tiles = ((M + 255) // 256) * ((N + 255) // 256)
+        s = 1
+        while s < SPLITK_MAX and tiles * 2 * s <= self.num_cus and (K // 64) // (2 * s) >= SPLITK_MIN_KTILES:
+            s *= 2
+        return s
 
     def gemm_nt_ln(self, A, B, C, bias=None, extra=None, ln_mean=None, ln_rstd=None, ln_colsum=None, stats_part=None, xb_out=None,
                    epi=EPI_RESID_LN_F32, group=0, flags=0):

@@ -1,0 +1,214 @@
+"""The box head's fully connected layers, Linear (+ ReLU), as GEMMs on channel-last RoI rows (include/clipself_hip.h).
+
+`nn.Linear(in, out)` followed by ReLU on bf16 rows X [rows, in] is one call of cs_gemm_nt with the ReLU epilogue (EPI_RELU_BF16):
+Y = relu(X . Wp^T + bias), rounded once to bf16.  The first FC of the head contracts the whole RoI map (in = C * P = 256 * 49 against 512
+outputs): few output tiles with a long contraction behind each, which the deterministic split-K form of that call serves (`splits`).
+
+`spatial=(C, P)` is mmdet's `x.flatten(1)` without moving data: the channel-last map [K, C, h, w] of the convolutions in front is the
+rows [K*P, C] = [K, P*C], and the weights are packed once as  Wp[o, p*C + c] = weight[o, c*P + p].  The backward is the same family:
+
+  dZ   dY where the saved Y > 0, else 0, cast to bf16 -- the one pointwise op left to torch (on [rows, out], at most 4 MB in the head);
+  dX = dZ . Wp        cs_gemm_nt(dZ, WpT), in x's dtype; with `spatial` returned as the channel-last map;
+  dW = dZ^T . X       cs_gemm_wgrad_tn; with `spatial` permuted back from (p, c) to (c, p) order (a torch permute of [out, P, C] fp32);
+  db                  a column sum of dZ (cs_colsum_bf16).
+
+No atomics: equal inputs give equal bits.  Operands are bf16, accumulation is fp32, parameter gradients are fp32.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from .conv import _rows_bf16
+from .det_backend import kernel_ops
+from .neck import EPI_BF16, EPI_F32, _version, _wgrad
+
+BF16, F32 = torch.bfloat16, torch.float32
+EPI_RELU_BF16 = 9
+ACTS = {None: EPI_BF16, "relu": EPI_RELU_BF16}
+
+# Whether fused=None takes the kernels where the backend has them: set from profiles/fc_bench.md by the rule of FUSED_CONV_DEFAULT -- on only
+# if the kernel route wins forward + backward against the faster torch variant (fp32, or bf16 autocast) at the training shape
+# (4096 x 12544 x 512).  It does: 270 us against 498 us under bf16 autocast (the faster one) and 1575 us in fp32, the form the detector runs;
+# the whole ConvFCBBoxHead forward + backward takes 6.9 ms against 8.2 ms with torch's FCs behind the same convolutions.
+FUSED_FC_DEFAULT = True
+
+
+def pack_weights(weight, spatial=None):
+    """(Wp bf16 [out, in], WpT bf16 [in, out rounded up to 64]) of a [out, in] weight.  With spatial=(C, P):
+    Wp[o, p*C + c] = weight[o, c*P + p], the order of channel-last rows.  WpT[i, o] = Wp[o, i] is the dgrad's B operand; its zero columns
+    pad the contraction to cs_gemm_nt's K tile."""
+    out, inf = weight.shape
+    wb = weight.detach().to(BF16)
+    if spatial is not None:
+        C, P = spatial
+        wb = wb.view(out, C, P).permute(0, 2, 1).reshape(out, P * C)
+    Wp = wb.contiguous()
+    outp = (out + 63) // 64 * 64
+    WpT = Wp.new_zeros(inf, outp)
+    WpT[:, :out] = Wp.t()
+    return Wp, WpT
+
+
+def relu_gate(Y, dY):
+    """dZ bf16 = dY where the saved output Y > 0, else 0: the ReLU's gate rides on the cast to bf16 that the gradient needs anyway.  The
+    mask comes from the layer's own output, never from dY."""
+    return torch.where(Y > 0, dY, torch.zeros((), dtype=dY.dtype, device=dY.device)).to(BF16)
+
+
+def unpack_wgrad(dWp, spatial=None):
+    """The packed weight gradient [out, in] in nn.Linear's layout: with spatial=(C, P) permuted back from (p, c) to (c, p) order."""
+    if spatial is None:
+        return dWp
+    C, P = spatial
+    return dWp.view(dWp.shape[0], P, C).permute(0, 2, 1).reshape(dWp.shape[0], C * P)
+
+
+class LinearAct(nn.Linear):
+    """nn.Linear(in_features, out_features) -- its parameters, names, initialisation and state dict -- followed by `act` (None or "relu"),
+    whose forward and backward run on the HIP kernels when the tensors live on a backend with LINEAR_ACT, in_features % 64 == 0 and
+    out_features % 8 == 0 (what cs_gemm_nt and cs_gemm_wgrad_tn take); F.linear (+ F.relu) otherwise.
+
+    spatial: (C, P) makes the layer take the 4-D map [K, C, h, w] with h*w == P and compute nn.Linear(x.flatten(1)).
+    fused:   True = the kernels or NotImplementedError, False = torch, None = FUSED_FC_DEFAULT where the kernels can run.
+    splits:  K slices of the forward GEMM; None = chosen by the library, an integer forces it (the benchmark, the tests).
+    forward(x): x [..., in_features] (or the map) fp32 / bf16 -> [..., out_features] of x's dtype; on the kernel route the values are bf16's."""
+
+    def __init__(self, in_features, out_features, bias=True, act=None, spatial=None, ops=None, fused=None, splits=None, **kw):
+        super().__init__(in_features, out_features, bias=bias, **kw)
+        assert act in ACTS, f"act is None or 'relu', got {act!r}"
+        assert spatial is None or (len(spatial) == 2 and spatial[0] * spatial[1] == in_features), \
+            f"spatial=(C, P) needs C * P == in_features, got {spatial} for {in_features}"
+        assert splits is None or splits >= 1, splits
+        self.act = act
+        self.spatial = None if spatial is None else (int(spatial[0]), int(spatial[1]))
+        self.ops = ops
+        self.fused = fused
+        self.splits = splits
+        self._wcache = None
+
+    def extra_repr(self):
+        return super().extra_repr() + f", act={self.act}, spatial={self.spatial}"
+
+    # ------------------------------------------------------------------------------------------ dispatch
+    def covered(self, x) -> bool:
+        """What the kernels cover: fp32 parameters, an fp32 / bf16 input of the layer's shape, in % 64 == 0, out % 8 == 0."""
+        if self.spatial is None:
+            shape_ok = x.dim() >= 1 and x.shape[-1] == self.in_features
+        else:
+            shape_ok = x.dim() == 4 and x.shape[1] == self.spatial[0] and x.shape[2] * x.shape[3] == self.spatial[1]
+        return (self.in_features % 64 == 0 and self.out_features % 8 == 0 and self.weight.dtype == F32 and x.dtype in (F32, BF16)
+                and shape_ok and x.numel() > 0 and x.device == self.weight.device)
+
+    def kernel_backend(self, x):
+        """The backend whose LINEAR_ACT kernels serve forward(x), or None (-> torch); NotImplementedError where fused=True cannot be met."""
+        ops, fused = self.ops, self.fused
+        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "LINEAR_ACT", False) \
+                and ops.empty((1,), F32).device == x.device:
+            k = ops if fused or FUSED_FC_DEFAULT else None            # a host backend (the tests' reference ops) serves host tensors
+        else:
+            k = kernel_ops(x, "LINEAR_ACT", ops, fused, FUSED_FC_DEFAULT)
+        if k is not None and not self.covered(x):
+            if fused:
+                raise NotImplementedError(f"fused=True: LinearAct({self.in_features}, {self.out_features}, spatial={self.spatial}) on {x.dtype} "
+                                          f"{tuple(x.shape)} is outside the kernels' coverage (in % 64 == 0, out % 8 == 0, fp32 parameters, "
+                                          "fp32 / bf16 input)")
+            return None
+        return k
+
+    def forward(self, x):
+        k = self.kernel_backend(x)
+        if k is None:
+            y = F.linear(x.flatten(1) if self.spatial is not None else x, self.weight, self.bias)
+            return F.relu(y) if self.act == "relu" else y
+        return _LinearActFn.apply(x, self.weight, self.bias, self, k)
+
+    # ------------------------------------------------------------------------------------------ operands
+    def gemm_weights(self):
+        """(Wp bf16 [out, in], WpT bf16 [in, out rounded up to 64], bias fp32 [out] | None), see pack_weights.  Rebuilt when the parameters'
+        version counters (or their storage) change."""
+        w, b = self.weight, self.bias
+        key = (w.data_ptr(), _version(w), w.device, None if b is None else (b.data_ptr(), _version(b)))
+        if self._wcache is None or self._wcache[0] != key:
+            with torch.no_grad():
+                Wp, WpT = pack_weights(w, self.spatial)
+                bias = None if b is None else b.detach().to(F32).contiguous()
+            self._wcache = (key, Wp, WpT, bias)
+        return self._wcache[1:]
+
+    def _splitk_ws(self, ops, M, N, K):
+        """(splits argument, fp32 workspace | None) of the forward GEMM: the module's own grow-only buffer of splits * M * N floats."""
+        s = self.splits if self.splits is not None else ops.gemm_nt_splits(M, N, K)
+        if s <= 1:
+            return 1, None
+        ws = self.__dict__.get("_splitk_buf")
+        if ws is None or ws.numel() < s * M * N or ws.device != self.weight.device:
+            ws = self.__dict__["_splitk_buf"] = ops.empty((s * M * N,), F32)
+        return (0 if self.splits is None else s), ws
+
+
+def _rows2d(ops, x, width):
+    """x [..., width] fp32 / bf16 -> bf16 rows [rows, width] with 16-byte aligned rows: a view where x allows it, one cast kernel for fp32."""
+    X = x.reshape(-1, width)
+    if X.dtype == BF16:
+        if X.stride(1) != 1 or X.stride(0) % 8 or X.data_ptr() % 16:
+            X = X.contiguous()
+        return X
+    out = ops.empty(tuple(X.shape), BF16)
+    ops.cast_f32_bf16(X.contiguous(), out)
+    return out
+
+
+class _LinearActFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, ops):
+        inf, out = mod.in_features, mod.out_features
+        Wp, _, b32 = mod.gemm_weights()
+        if mod.spatial is not None:
+            X = _rows_bf16(ops, x).reshape(x.shape[0], inf)            # [K*P, C] seen as [K, P*C]: no data moves for a channel-last bf16 map
+        else:
+            X = _rows2d(ops, x, inf)
+        rows = X.shape[0]
+        Y = ops.empty((rows, out), BF16)
+        splits, ws = mod._splitk_ws(ops, rows, out, inf)
+        ops.gemm_nt(X, Wp, Y, b32, extra=ws, epi=ACTS[mod.act], splits=splits)
+        ctx.mod, ctx.ops, ctx.x_shape, ctx.x_dtype, ctx.has_bias = mod, ops, tuple(x.shape), x.dtype, bias is not None
+        ctx.save_for_backward(X, Y)
+        y = Y if x.dtype == BF16 else Y.to(x.dtype)
+        return y.view(rows, out) if mod.spatial is not None else y.view(*x.shape[:-1], out)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        mod, ops = ctx.mod, ctx.ops
+        inf, out = mod.in_features, mod.out_features
+        X, Y = ctx.saved_tensors
+        rows = X.shape[0]
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+        dY = d_out.reshape(rows, out)
+        dZ = relu_gate(Y, dY) if mod.act == "relu" else dY.to(BF16)
+        outp = (out + 63) // 64 * 64
+        if outp != out:                                                # zero columns pad the dgrad's contraction to the K tile
+            dZp = ops.zeros((rows, outp), BF16)
+            dZp[:, :out] = dZ
+            dZ = dZp[:, :out]
+        else:
+            dZp = dZ = dZ.contiguous()
+        dx = dw = db = None
+        if need_x:
+            _, WpT, _ = mod.gemm_weights()
+            dX = ops.empty((rows, inf), ctx.x_dtype)
+            ops.gemm_nt(dZp, WpT, dX, None, epi=EPI_F32 if ctx.x_dtype == F32 else EPI_BF16)
+            if mod.spatial is not None:
+                K, C, h, w = ctx.x_shape
+                dx = dX.view(K, h, w, C).permute(0, 3, 1, 2)             # the channel-last map: the batch norm in front takes it in place
+            else:
+                dx = dX.view(ctx.x_shape)
+        if need_w:
+            dWp = ops.zeros((out, inf), F32)
+            _wgrad(ops, mod, dZ, X, dWp)
+            dw = unpack_wgrad(dWp, mod.spatial)
+        if need_b:
+            db = ops.zeros((out,), F32)
+            ops.colsum_bf16(dZ, db)
+        return dx, dw, db, None, None

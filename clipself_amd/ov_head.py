@@ -7,7 +7,8 @@
             with the detector's softmax as det^(1-alpha) * vlm^alpha on base classes and det^(1-beta) * vlm^beta on novel classes;
   :290-347 (FViTTransferBBoxHead)  the same with one exponent for all classes (seen_classes=None here).
 
-The convolutions and linears in front of `cls_score` (ConvFCBBoxHead), FPN and RPN are mmdet's and stay there: this module takes the
+The convolutions and linears in front of `cls_score` are bbox_head.ConvFCBBoxHead (mmdet's module of that name on this project's layers);
+FPN and RPN are mmdet's and stay there: this module takes the
 class branch's output and the backbone's dense map (fvit.EvaCLIPViT's fifth output) and returns the blended scores [K, C].  `get_bboxes`
 (:123-164) turns them into detections through det_post (box decoding, class-aware NMS and the cut as HIP kernels, no mmcv / mmdet).
 

@@ -31,7 +31,21 @@ const char* cs_last_error(void);
  *      4 f32 atomic accumulate (split-K allowed: `splits` >= 1, or <= 0 = chosen by the library) |
  *      5 patch embed: out row = row + row/group + 1, value += extra[(row%group+1)*ldc + col]   (cls/pos layout :540-543) |
  *      7 bf16 = GELU(acc+bias), 8 bf16 = QuickGELU(acc+bias): c_fc + activation of the OpenAI-CLIP ViT MLP
- *        (src/open_clip/transformer.py:209-213 `mlp`, :31-34 `QuickGELU`)
+ *        (src/open_clip/transformer.py:209-213 `mlp`, :31-34 `QuickGELU`) |
+ *      9 bf16 = ReLU(acc+bias), v < 0 ? 0 : v (a NaN passes): the detector box head's Linear + ReLU
+ *        (F-ViT/models/fvit_head.py:82-83, 95-96, 104-105: shared_fcs, cls_fcs, reg_fcs)
+ * splits: 1 everywhere except
+ *      epi 4: the atomic split-K above;
+ *      epi 0 / 9: deterministic split-K for skinny, deep problems (the box head's 4096 x 512 outputs behind K = 12 544).  `splits` > 1, or
+ *        <= 0 = chosen by the library, cuts the K / 64 K tiles into `splits` contiguous slices of ceil(K / 64 / splits) tiles; `extra` is
+ *        then an fp32 WORKSPACE of at least splits * M * N floats, 16-byte aligned, that receives each slice's partial product
+ *        [M, N] (contiguous, slice-major); one pass adds the partials in ascending slice order, adds `bias` once, applies the ReLU
+ *        of epi 9 and writes the bf16 rows at ldc (columns >= N of a padded C stay untouched).  No atomics: the same (M, N, K, splits)
+ *        gives the same bits.  The library's choice for splits <= 0 is a pure function of the shape and the device:
+ *            s = 1;  while (s < 8  &&  ceil(M/256) * ceil(N/256) * 2s <= compute units  &&  (K/64) / (2s) >= 16)  s *= 2;
+ *        so a caller sizes the workspace with the same expression (cs_num_compute_units); where it yields 1 the call is the plain one
+ *        and `extra` is not read.  Errors (-1): splits > K / 64; `extra` NULL or misaligned where more than one slice runs;
+ *        splits != 1 on any other epilogue (or on cs_gemm_nt_ln's folded LayerNorm).
  * flags bit0: use register staging instead of the global_load_lds DMA path; bits 4-7: force a tile schedule (0 = heuristic; 11 = the
  * streaming persistent kernel with register-level epilogues, the default for the bf16 / QuickGELU / SwiGLU epilogues of large problems);
  * bits 20-27: compute units the persistent kernels leave free (0 = use all 256; data-parallel runs reserve a few for RCCL's kernels). */
