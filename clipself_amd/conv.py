@@ -199,3 +199,127 @@ class _Conv3x3Fn(torch.autograd.Function):
             db = ops.zeros((Cout,), F32)
             ops.colsum_bf16(dY, db)
         return dx, dw, db, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------ 1 x 1 convolutions (the FPN's laterals)
+# Whether fused=None takes the GEMMs where the backend has them: set from profiles/fpn_bench.md (the laterals with their norms, forward +
+# backward) by the rule of FUSED_CONV_DEFAULT.  Off: the kernel laterals take 2.53 / 5.59 / 7.14 ms (B/16 640^2, B/16 1024^2, L/14-336 896^2)
+# against 1.82 / 4.06 / 5.01 ms of torch under bf16 autocast on channels-last inputs (0.70 - 0.73 x; 1.45 - 1.60 x against torch fp32).
+# The GEMMs are not the cost: an fp32 NCHW input pays the rows conversion (10 - 11 %) and, since a layer returns its input's type, fp32
+# maps through the norm and both gradients, twice the bytes of autocast's bf16 ones (the per-stage table of profiles/fpn_bench.md).
+FUSED_CONV1X1_DEFAULT = False
+
+
+def pack_weights_1x1(weight):
+    """(W bf16 [Cout, Cin], WT bf16 [Cin, Cout rounded up to 64]) of a [Cout, Cin, 1, 1] weight.  WT[ci, co] = W[co, ci] is the input
+    gradient's B operand; its zero columns pad that contraction to cs_gemm_nt's K tile (as linear.pack_weights)."""
+    Cout, Cin = weight.shape[:2]
+    Wm = weight.detach().to(BF16).reshape(Cout, Cin).contiguous()
+    WT = Wm.new_zeros(Cin, (Cout + 63) // 64 * 64)
+    WT[:, :Cout] = Wm.t()
+    return Wm, WT
+
+
+class Conv1x1(nn.Conv2d):
+    """nn.Conv2d(Cin, Cout, 1) -- its parameters, names, initialisation and state dict -- as one GEMM on channel-last rows,
+    Y[N*H*W, Cout] = X[N*H*W, Cin] . W^T + bias, when the tensors live on a backend with FPN_TOPDOWN, Cin % 64 == 0 and Cout % 8 == 0 (what
+    cs_gemm_nt and cs_gemm_wgrad_tn take); F.conv2d otherwise.  No kernel of its own: cs_gemm_nt forward and for the input gradient,
+    cs_gemm_wgrad_tn for the weight gradient, cs_colsum_bf16 for the bias gradient.
+
+    fused: True = the kernels or NotImplementedError, False = F.conv2d, None = FUSED_CONV1X1_DEFAULT where the kernels can run.
+    forward(x): x [N, Cin, H, W] fp32 or bf16 of any strides -> [N, Cout, H, W] of x's dtype with channel-last strides (kernel route)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=1, stride=1, padding=0, bias=True, ops=None, fused=None, **kw):
+        super().__init__(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)
+        assert self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and self.dilation == (1, 1) \
+            and self.groups == 1, "Conv1x1 is Conv2d(kernel_size=1, stride=1, padding=0) and nothing else"
+        self.ops = ops
+        self.fused = fused
+        self._wcache = None
+
+    # ------------------------------------------------------------------------------------------ dispatch
+    def covered(self, x) -> bool:
+        """What the kernels cover: fp32 parameters, a 4-D fp32 / bf16 input, Cin % 64 == 0, Cout % 8 == 0."""
+        return (self.in_channels % 64 == 0 and self.out_channels % 8 == 0 and self.weight.dtype == F32 and x.dim() == 4
+                and x.dtype in (F32, BF16) and x.shape[1] == self.in_channels and x.numel() > 0 and x.device == self.weight.device)
+
+    def kernel_backend(self, x):
+        """The backend whose GEMMs serve forward(x), or None (-> F.conv2d); NotImplementedError where fused=True cannot be met."""
+        ops, fused = self.ops, self.fused
+        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "FPN_TOPDOWN", False) \
+                and ops.empty((1,), F32).device == x.device:
+            k = ops if fused or FUSED_CONV1X1_DEFAULT else None       # a host backend (the tests' reference ops) serves host tensors
+        else:
+            k = kernel_ops(x, "FPN_TOPDOWN", ops, fused, FUSED_CONV1X1_DEFAULT)
+        if k is not None and not self.covered(x):
+            if fused:
+                raise NotImplementedError(f"fused=True: Conv1x1({self.in_channels}, {self.out_channels}) on {x.dtype} {tuple(x.shape)} is outside "
+                                          "the kernels' coverage (Cin % 64 == 0, Cout % 8 == 0, fp32 parameters, fp32 / bf16 input)")
+            return None
+        return k
+
+    def forward(self, x):
+        k = self.kernel_backend(x)
+        if k is None:
+            return F.conv2d(x, self.weight, self.bias)
+        return _Conv1x1Fn.apply(x, self.weight, self.bias, self, k)
+
+    # ------------------------------------------------------------------------------------------ operands
+    def gemm_weights(self):
+        """(W bf16 [Cout, Cin], WT bf16 [Cin, Cout rounded up to 64], bias fp32 [Cout] | None), see pack_weights_1x1.  Rebuilt when the
+        parameters' version counters (or their storage) change."""
+        w, b = self.weight, self.bias
+        key = (w.data_ptr(), _version(w), w.device, None if b is None else (b.data_ptr(), _version(b)))
+        if self._wcache is None or self._wcache[0] != key:
+            with torch.no_grad():
+                Wm, WT = pack_weights_1x1(w)
+                bias = None if b is None else b.detach().to(F32).contiguous()
+            self._wcache = (key, Wm, WT, bias)
+        return self._wcache[1:]
+
+
+class _Conv1x1Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, ops):
+        N, Cin, H, W = x.shape
+        Cout = mod.out_channels
+        Wm, _, b32 = mod.gemm_weights()
+        X = _rows_bf16(ops, x)
+        Y = ops.empty((N * H * W, Cout), x.dtype)
+        ops.gemm_nt(X, Wm, Y, b32, epi=EPI_F32 if x.dtype == F32 else EPI_BF16)
+        ctx.mod, ctx.ops, ctx.geom, ctx.x_dtype = mod, ops, (N, H, W), x.dtype
+        ctx.has_bias = bias is not None
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(X)
+        return Y.view(N, H, W, Cout).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        mod, ops = ctx.mod, ctx.ops
+        N, H, W = ctx.geom
+        Cin, Cout, M = mod.in_channels, mod.out_channels, N * H * W
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+        if d_out.dtype not in (F32, BF16):
+            d_out = d_out.to(F32)
+        dY = _rows_bf16(ops, d_out)
+        dx = dw = db = None
+        if need_x:
+            _, WT, _ = mod.gemm_weights()
+            Kp = WT.shape[1]
+            if Kp != Cout:                                             # zero columns pad the contraction to the K tile
+                dYp = ops.zeros((M, Kp), BF16)
+                dYp[:, :Cout] = dY
+            else:
+                dYp = dY
+            dX = ops.empty((M, Cin), ctx.x_dtype)
+            ops.gemm_nt(dYp, WT, dX, None, epi=EPI_F32 if ctx.x_dtype == F32 else EPI_BF16)
+            dx = dX.view(N, H, W, Cin).permute(0, 3, 1, 2)
+        if need_w:
+            (X,) = ctx.saved_tensors
+            dWm = ops.zeros((Cout, Cin), F32)
+            _wgrad(ops, mod, dY, X, dWm)
+            dw = dWm.view(Cout, Cin, 1, 1)
+        if need_b:
+            db = ops.zeros((Cout,), F32)
+            ops.colsum_bf16(dY, db)
+        return dx, dw, db, None, None

@@ -509,6 +509,115 @@ __global__ __launch_bounds__(256) void nchw_to_rows_kernel(const TI* __restrict_
     }
 }
 
+// The FPN's top-down step on channel-last rows (cs_transpose_bf16 forms 7 / 8): nearest-neighbour upsampling by two
+// added into the finer level, and its adjoint, the sum of each 2 x 2 block.  coarse = rows [B*h*w, C], fine = rows [B*2h*2w, C], each
+// with its own row stride and element type; coarse pixel (b, i, j) owns the fine pixels (b, 2i + di, 2j + dj).  Both are streams: a
+// thread owns one channel group (VEC channels: 8 = 16 bytes of both bf16 maps, 4 = 16 bytes of an fp32 map beside 8 bytes of a bf16 one,
+// 1 = any C, stride or alignment) of one COARSE pixel and touches that pixel's four fine pixels, so the coarse value moves once and
+// every output element has exactly one writer (the in-place accumulate of form 7 reads an element only in the thread that writes it).
+// Neighbouring threads take neighbouring groups of a pixel, then the next pixel of the grid row: a wave reads whole coarse segments
+// and, per (di, dj), every second fine pixel, whose dj = 1 neighbour the same lanes write next.  A capped grid walks the items with a
+// grid-stride loop; offsets are 64-bit.  One rounding, at the output's type.
+struct TopDownGeom {
+    unsigned items, G;        // B * R * G work items, channel groups per pixel
+    int R, w;                 // coarse pixels per image, coarse grid width
+};
+template <bool BF, int VEC>
+__device__ __forceinline__ void td_load(const void* p, size_t off, float (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        v[0] = BF ? bf2f(((const __bf16*)p)[off]) : ((const float*)p)[off];
+    } else if constexpr (!BF) {
+        const float4 t = *(const float4*)((const float*)p + off);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else if constexpr (VEC == 4) {
+        U64 t;
+        t.u = *(const uint2*)((const __bf16*)p + off);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = bf2f(t.e[e]);
+    } else {
+        U128 t;
+        t.u = *(const uint4*)((const __bf16*)p + off);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = bf2f(t.e[e]);
+    }
+}
+template <bool BF, int VEC>
+__device__ __forceinline__ void td_store(void* p, size_t off, const float (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        if constexpr (BF) ((__bf16*)p)[off] = f2bf(v[0]);
+        else ((float*)p)[off] = v[0];
+    } else if constexpr (!BF) {
+        *(float4*)((float*)p + off) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if constexpr (VEC == 4) {
+        U64 t;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t.e[e] = f2bf(v[e]);
+        *(uint2*)((__bf16*)p + off) = t.u;
+    } else {
+        U128 t;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) t.e[e] = f2bf(v[e]);
+        *(uint4*)((__bf16*)p + off) = t.u;
+    }
+}
+// item t -> the offsets of its coarse group and of the (0, 0) fine group
+__device__ __forceinline__ void td_offsets(const TopDownGeom& g, unsigned t, int vec, long ldc, long ldf, size_t* oc, size_t* of) {
+    const unsigned pix = t / g.G, grp = t - pix * g.G;
+    const unsigned b = pix / (unsigned)g.R, p = pix - b * (unsigned)g.R, i = p / (unsigned)g.w, j = p - i * (unsigned)g.w;
+    *oc = (size_t)pix * (size_t)ldc + (size_t)grp * vec;
+    *of = ((size_t)b * 4u * (size_t)g.R + (size_t)(2u * i) * (2u * (size_t)g.w) + 2u * j) * (size_t)ldf + (size_t)grp * vec;
+}
+
+// form 7: fine[b, 2i + di, 2j + dj, c] = rnd(acc ? fine + coarse[b, i, j, c] : coarse[b, i, j, c])
+template <bool CB, bool FB, int VEC>
+__global__ __launch_bounds__(256) void upsample2x_add_kernel(const void* __restrict__ coarse, long ldc, void* fine, long ldf, TopDownGeom g,
+                                                             int acc) {
+    const size_t down = (size_t)2 * g.w * (size_t)ldf;                 // one fine grid row
+    for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < g.items; t += gridDim.x * 256u) {
+        size_t oc, of;
+        td_offsets(g, t, VEC, ldc, ldf, &oc, &of);
+        const size_t o[4] = {of, of + (size_t)ldf, of + down, of + down + (size_t)ldf};
+        float c[VEC], f[4][VEC];
+        td_load<CB, VEC>(coarse, oc, c);
+        if (acc) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) td_load<FB, VEC>(fine, o[q], f[q]);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) f[q][e] += c[e];
+                td_store<FB, VEC>(fine, o[q], f[q]);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) td_store<FB, VEC>(fine, o[q], c);
+        }
+    }
+}
+
+// form 8: coarse[b, i, j, c] = rnd(acc ? coarse + s : s),  s = ((f00 + f01) + f10) + f11 of the four fine pixels, in fp32
+template <bool CB, bool FB, int VEC>
+__global__ __launch_bounds__(256) void pool2x_kernel(const void* __restrict__ fine, long ldf, void* coarse, long ldc, TopDownGeom g, int acc) {
+    const size_t down = (size_t)2 * g.w * (size_t)ldf;
+    for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < g.items; t += gridDim.x * 256u) {
+        size_t oc, of;
+        td_offsets(g, t, VEC, ldc, ldf, &oc, &of);
+        const size_t o[4] = {of, of + (size_t)ldf, of + down, of + down + (size_t)ldf};
+        float f[4][VEC], s[VEC];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) td_load<FB, VEC>(fine, o[q], f[q]);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s[e] = ((f[0][e] + f[1][e]) + f[2][e]) + f[3][e];
+        if (acc) {
+            float c[VEC];
+            td_load<CB, VEC>(coarse, oc, c);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) s[e] = c[e] + s[e];
+        }
+        td_store<CB, VEC>(coarse, oc, s);
+    }
+}
+
 // out[n] += sum_m x[m, n]   (bias gradients; bf16 in, f32 out).  grid.x tiles columns, grid.y splits rows into blocks whose partial sums
 // go to a workspace row each; colsum_reduce_kernel adds them up in a fixed order.
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const __bf16* __restrict__ x, long ldx, float* __restrict__ out, int M, int N,
@@ -729,7 +838,56 @@ static int deconv_rows_launch(const void* in, long ld_in, void* out, long ld_out
     CS_LAUNCH_CHECK();
     return 0;
 }
-// form 0: the padded bf16 transpose above (batch must be 1).  forms 4 / 5 (low byte): deconv_rows_launch above.  form 1 / 2: the token taps of a frozen dense pass -- in = the fp32 residual
+// Forms 7 / 8 of cs_transpose_bf16 (low byte of `form`): the FPN's top-down add and its adjoint on channel-last rows.  form bit 8 = 1
+// (the factor 2), bit 9 = accumulate into `out`, bit 10 / 11 = element type of the coarse / fine rows (0 fp32, 1 bf16), bits 12-31 = the
+// coarse grid width w; R = h * w of the coarse grid, Cc = C, batch = B.  Form 7: in = coarse, out = fine; form 8: in = fine, out = coarse.
+// The grid is TOPDOWN_BLOCKS_PER_CU workgroups per compute unit at the most: it follows from the arguments and the CU count alone.
+constexpr int TOPDOWN_BLOCKS_PER_CU = 8;                   // 32 waves per CU: every workgroup resident at once
+template <bool CB, bool FB, int VEC>
+static void topdown_launch_typed(bool pool, const void* in, long ld_in, void* out, long ld_out, const TopDownGeom& g, int acc, dim3 grid,
+                                 hipStream_t stream) {
+    if (pool) hipLaunchKernelGGL((pool2x_kernel<CB, FB, VEC>), grid, dim3(256), 0, stream, in, ld_in, out, ld_out, g, acc);
+    else hipLaunchKernelGGL((upsample2x_add_kernel<CB, FB, VEC>), grid, dim3(256), 0, stream, in, ld_in, out, ld_out, g, acc);
+}
+static int topdown_launch(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, hipStream_t stream) {
+    const bool pool = (form & 255) == 8;
+    const int s_bit = (form >> 8) & 1, acc = (form >> 9) & 1, cb = (form >> 10) & 1, fb = (form >> 11) & 1;
+    const int w = (int)((unsigned)form >> 12);
+    const long ldc = pool ? ld_out : ld_in, ldf = pool ? ld_in : ld_out;
+    CS_CHECK_ARG(in && out && s_bit == 1 && R > 0 && Cc > 0 && batch > 0 && w > 0 && R % w == 0 && ldc >= Cc && ldf >= Cc &&
+                     (long)batch * R <= 0x7fffffffL / Cc,
+                 "cs_transpose_bf16 (FPN top-down, form %d): bit 8 = %d (1: the factor 2 is the only one) batch=%d coarse pixels=%d (a multiple "
+                 "of w=%d, w > 0) C=%d (batch * pixels * C <= 2^31 - 1) coarse stride=%ld fine stride=%ld (each >= C)",
+                 form & 255, s_bit, batch, R, w, Cc, ldc, ldf);
+    const void* coarse = pool ? out : in;
+    const void* fine = pool ? in : out;
+    // channels per thread: 16 bytes of the wider type where C, both strides and both bases allow whole vectors, one element otherwise
+    int vec = (cb && fb) ? 8 : 4;
+    const uintptr_t ac = (uintptr_t)coarse, af = (uintptr_t)fine;
+    if (Cc % vec || ldc % vec || ldf % vec || ac % (vec * (cb ? 2 : 4)) || af % (vec * (fb ? 2 : 4))) vec = 1;
+    const unsigned G = (unsigned)(Cc / vec);
+    const TopDownGeom g{(unsigned)((long)batch * R * G), G, R, w};
+    long blocks = ((long)g.items + 255) / 256;
+    const long cap = (long)TOPDOWN_BLOCKS_PER_CU * cs_num_compute_units();
+    if (blocks > cap) blocks = cap;
+    const dim3 grid((unsigned)blocks);
+#define CS_TOPDOWN(CB, FB, VEC) topdown_launch_typed<CB, FB, VEC>(pool, in, ld_in, out, ld_out, g, acc, grid, stream)
+    if (vec == 8) CS_TOPDOWN(true, true, 8);
+    else if (vec == 4) {
+        if (cb) CS_TOPDOWN(true, false, 4);
+        else if (fb) CS_TOPDOWN(false, true, 4);
+        else CS_TOPDOWN(false, false, 4);
+    } else {
+        if (cb && fb) CS_TOPDOWN(true, true, 1);
+        else if (cb) CS_TOPDOWN(true, false, 1);
+        else if (fb) CS_TOPDOWN(false, true, 1);
+        else CS_TOPDOWN(false, false, 1);
+    }
+#undef CS_TOPDOWN
+    CS_LAUNCH_CHECK();
+    return 0;
+}
+// form 0: the padded bf16 transpose above (batch must be 1).  forms 4 / 5 (low byte): deconv_rows_launch above.  forms 7 / 8 (low byte): topdown_launch above.  form 1 / 2: the token taps of a frozen dense pass -- in = the fp32 residual
 // stream x[batch * (R + 1), ld_in] (R = h * w patch tokens per image behind its CLS row, Cc = C channels, ld_in >= C), out = [batch, Cc, R]
 // contiguous (ld_out == R), fp32 (1) or bf16 (2): out[b, c, p] = x[b * (R + 1) + 1 + p, c]  (tokens_to_nchw_kernel).
 extern "C" int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, hipStream_t stream) {
@@ -741,8 +899,10 @@ extern "C" int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_
         return 0;
     }
     if ((form & 255) == 4 || (form & 255) == 5) return deconv_rows_launch(in, ld_in, out, ld_out, R, Cc, form, batch, stream);
+    if ((form & 255) == 7 || (form & 255) == 8) return topdown_launch(in, ld_in, out, ld_out, R, Cc, form, batch, stream);
     CS_CHECK_ARG(form == 1 || form == 2,
-                 "cs_transpose_bf16: form %d (0 bf16 transpose, 1 / 2 token taps to fp32 / bf16, low byte 4 / 5 rows <-> NCHW of the 2x2 deconvolution)", form);
+                 "cs_transpose_bf16: form %d (0 bf16 transpose, 1 / 2 token taps to fp32 / bf16, low byte 4 / 5 rows <-> NCHW of the 2x2 deconvolution, "
+                 "low byte 7 / 8 the FPN's top-down add and its adjoint)", form);
     CS_CHECK_ARG(in && out && R > 0 && Cc > 0 && batch > 0 && batch <= 65535 && ld_in >= Cc && ld_out == R && (Cc + 63) / 64 <= 65535,
                  "cs_transpose_bf16 (token taps): batch=%d (1..65535) tokens=%d C=%d ld_in=%ld (>= C) ld_out=%ld (== tokens)", batch, R, Cc, ld_in, ld_out);
     const dim3 grid((R + 63) / 64, (Cc + 63) / 64, batch);

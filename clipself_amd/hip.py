@@ -274,7 +274,8 @@ class HipOps:
     CONV3X3 = True                      # conv3x3 / im2col3x3: Conv2d(Cin, Cout, 3, padding=1) on channel-last rows as an implicit GEMM (conv.Conv3x3)
     BATCHNORM = True                    # bn_stats / bn_finalize / bn_apply / bn_bwd_reduce / bn_bwd_apply: batch norm (+ ReLU) on channel-last rows (norm_act.BatchNormAct2d)
     LINEAR_ACT = True                   # gemm_nt(epi=EPI_RELU_BF16, splits=, extra=workspace): Linear + ReLU with deterministic split-K (linear.LinearAct)
-    BOX_SCORES = True                 # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
+    FPN_TOPDOWN = True                  # upsample2x_add / pool2x: the FPN's top-down add and its adjoint on channel-last rows; Conv1x1 on gemm_nt (fpn.FPN)
+    BOX_SCORES = True              # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
         self.lib = load_library()
@@ -830,6 +831,31 @@ class HipOps:
         assert rows.dtype == torch.bfloat16
         form = self._deconv_form(5, rows, x, B, h, w, C, s, off)
         self._ok(self.lib.cs_transpose_bf16(_p(x), 0, _p(rows), rows.stride(0), h * w, C, form, B, self._stream()), "cs_transpose_bf16")
+
+    @staticmethod
+    def _topdown_form(form, coarse, fine, B, h, w, C, accumulate):
+        """Checks shared by upsample2x_add / pool2x -> the packed `form` of cs_transpose_bf16 (include/clipself_hip.h)."""
+        assert min(B, h, w, C) >= 1 and w < (1 << 20) and B * h * w * C < (1 << 31)
+        assert coarse.dim() == 2 and coarse.stride(1) == 1 and coarse.shape[0] == B * h * w and coarse.shape[1] == C <= coarse.stride(0)
+        assert fine.dim() == 2 and fine.stride(1) == 1 and fine.shape[0] == 4 * B * h * w and fine.shape[1] == C <= fine.stride(0)
+        return form | 1 << 8 | int(bool(accumulate)) << 9 | _dt(coarse) << 10 | _dt(fine) << 11 | w << 12
+
+    def upsample2x_add(self, coarse, fine, B, h, w, C, accumulate=True):
+        """coarse fp32 / bf16 rows [B*h*w, C], fine fp32 / bf16 rows [B*2h*2w, C] (each with its own row stride >= C), in place:
+        fine[b, 2i+di, 2j+dj, c] = rnd((fine[b, 2i+di, 2j+dj, c] if accumulate else 0) + coarse[b, i, j, c]) -- form 7 of cs_transpose_bf16:
+        the FPN's laterals[i - 1] += F.interpolate(laterals[i], scale_factor=2, mode='nearest') on channel-last maps.  One rounding."""
+        self._chk(coarse, fine)
+        form = self._topdown_form(7, coarse, fine, B, h, w, C, accumulate)
+        self._ok(self.lib.cs_transpose_bf16(_p(coarse), coarse.stride(0), _p(fine), fine.stride(0), h * w, C, form, B, self._stream()),
+                 "cs_transpose_bf16")
+
+    def pool2x(self, fine, coarse, B, h, w, C, accumulate=False):
+        """Its adjoint, form 8: coarse[b, i, j, c] = rnd((coarse[b, i, j, c] if accumulate else 0) + s) with
+        s = ((fine[b, 2i, 2j, c] + fine[b, 2i, 2j+1, c]) + fine[b, 2i+1, 2j, c]) + fine[b, 2i+1, 2j+1, c] in fp32."""
+        self._chk(fine, coarse)
+        form = self._topdown_form(8, coarse, fine, B, h, w, C, accumulate)
+        self._ok(self.lib.cs_transpose_bf16(_p(fine), fine.stride(0), _p(coarse), coarse.stride(0), h * w, C, form, B, self._stream()),
+                 "cs_transpose_bf16")
 
     def transpose_bf16_batched(self, pairs):
         """[(inp [R, C], out [C, ld_out >= R]), ...] -> every out = inp^T (zero padded) in ONE launch.  The device descriptor table is

@@ -20,7 +20,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
-from .conv import Conv3x3, _is_channel_last
+from .conv import Conv1x1, Conv3x3, _is_channel_last
 from .det_backend import kernel_ops
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -184,13 +184,16 @@ class ConvModule(nn.Module):
     """The F-ViT form of mmcv's ConvModule(in_channels, out_channels, 3, padding=1, norm_cfg=dict(type='SyncBN'), act_cfg=dict(type='ReLU')):
     `conv` (Conv3x3; bias=False when a norm follows, mmcv's bias='auto') then `bn` (BatchNormAct2d carrying the activation), the order and
     the names of mmcv/cnn/bricks/conv_module.py, so a reference checkpoint's ....conv.weight, ....bn.weight, ....bn.bias,
-    ....bn.running_mean, ....bn.running_var and ....bn.num_batches_tracked load with strict=True."""
+    ....bn.running_mean, ....bn.running_var and ....bn.num_batches_tracked load with strict=True.  kernel_size=1 builds the same module
+    around Conv1x1 (padding 0): with act=None, the lateral convolutions of fpn.FPN."""
 
-    def __init__(self, in_channels, out_channels, norm=True, act="relu", ops=None, fused=None):
+    def __init__(self, in_channels, out_channels, norm=True, act="relu", ops=None, fused=None, kernel_size=3):
         super().__init__()
         assert act in ACTS, f"act is None or 'relu', got {act!r}"
+        assert kernel_size in (1, 3), f"kernel_size is 1 or 3, got {kernel_size!r}"
         self.act = act
-        self.conv = Conv3x3(in_channels, out_channels, bias=not norm, ops=ops, fused=fused)
+        conv = Conv3x3 if kernel_size == 3 else Conv1x1               # kernel_size=1, act=None: the FPN's laterals (mmcv's act_cfg=None)
+        self.conv = conv(in_channels, out_channels, bias=not norm, ops=ops, fused=fused)
         self.bn = BatchNormAct2d(out_channels, act=act, ops=ops, fused=fused) if norm else None
 
     def forward(self, x):

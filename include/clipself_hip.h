@@ -266,7 +266,24 @@ int cs_cast_f32_bf16(const float* x, void* y, long n, cs_stream_t stream);
  * >= s*s*C.  fp32 -> bf16 rounds to nearest even, bf16 -> fp32 is exact.  Form 4 never reads CLS rows or columns past s*s*C, form 5
  * never writes columns past s*s*C.  16-byte accesses on the rows side where the stride and C are multiples of 4 (fp32) / 8 (bf16), on the
  * NCHW side where s*w is, with 16-byte aligned pointers; one element per lane otherwise.  Plain loads and stores, no workspace.
- * Any other form (3, or a low byte above 5) returns -1. */
+ * forms 7 / 8 (the LOW BYTE of `form`), the top-down step of a feature pyramid on channel-last rows (mmdet FPN.forward:
+ * laterals[i - 1] += F.interpolate(laterals[i], mode='nearest'), clipself_amd/fpn.py) and its adjoint.  coarse = rows [batch*h*w, C],
+ * fine = rows [batch*2h*2w, C], pixel-major (b, y, x), each map with its own row stride >= C and its own element type; offsets are 64-bit.
+ * R = h * w of the COARSE grid (a multiple of w; h != w is fine), Cc = C, batch = B.  The other bits of `form`: bit 8 = 1 (the factor 2 is
+ * the only one; 0 returns -1), bit 9 = accumulate (1: `out` is read and added to, 0: `out` is overwritten), bit 10 / 11 = element type of
+ * the coarse / fine rows (0 fp32, 1 bf16), bits 12-31 = the coarse grid width w.
+ *   form 7, in = coarse (ld_in), out = fine (ld_out): for (di, dj) in {0, 1}^2
+ *       out[b, 2i+di, 2j+dj, c] = rnd(acc ? float(out[b, 2i+di, 2j+dj, c]) + float(in[b, i, j, c]) : float(in[b, i, j, c]))
+ *   form 8, in = fine (ld_in), out = coarse (ld_out): with f(di, dj) = float(in[b, 2i+di, 2j+dj, c]) and
+ *       s = ((f(0,0) + f(0,1)) + f(1,0)) + f(1,1) in fp32, in that order,   out[b, i, j, c] = rnd(acc ? float(out[b, i, j, c]) + s : s)
+ * One rounding, at out's type (bf16: to nearest even); bf16 -> fp32 is exact.  Every output element is written exactly once per call and
+ * read (bit 9) only by its writer, so form 7 accumulates in place without a race.  Columns >= C of a padded row are never read and never
+ * written.  Plain loads and stores, no atomics, no workspace, nothing read back; the grid follows from the arguments and the device's
+ * compute-unit count alone (a capped grid-stride stream, 8 workgroups of 256 threads per compute unit at the most).  A thread moves one
+ * 16-byte channel group of a coarse pixel and of its four fine pixels -- 8 channels when both maps are bf16, 4 otherwise -- where C and
+ * both strides are multiples of that count and both pointers are aligned to their access; one element per lane otherwise (any C >= 1).
+ * Returns -1 (nothing launched) for w == 0, R no multiple of w, a stride below C, bit 8 clear, or batch * R * C > 2^31 - 1.
+ * Any other form (3, 6, or a low byte above 8) returns -1. */
 int cs_transpose_bf16(const void* in, long ld_in, void* out, long ld_out, int R, int Cc, int form, int batch, cs_stream_t stream);
 /* `count` such transposes in one launch (the W^T shadows the dgrad GEMMs read are rebuilt after every AdamW step: eva_vit_model.py:99-103,
  * 177-179,218-219 are the linears; 49 matrices per step for B/16).  desc = DEVICE array of 48-byte records
