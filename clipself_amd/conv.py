@@ -323,3 +323,196 @@ class _Conv1x1Fn(torch.autograd.Function):
             db = ops.zeros((Cout,), F32)
             ops.colsum_bf16(dY, db)
         return dx, dw, db, None, None
+
+
+# ------------------------------------------------------------------------------------------------ thin 1 x 1 convolutions (RPN and mask heads)
+# Whether fused=None takes the thin kernels where the backend has them, by the rule of FUSED_CONV_DEFAULT: on only if the kernel route wins
+# forward + backward against the faster torch variant at every measured shape.  It does not (profiles/thin_heads_bench.md, B = 8): the
+# heads alone win -- rpn_cls | rpn_reg 1.60 / 1.66 x (640^2 / 1024^2) on fp32 channel-last maps, the mask head's tail 1.54 x, the whole
+# FCNMaskHead 7.86 against 10.27 ms of torch under bf16 autocast -- but the whole RPNHead over five levels ties autocast at 640^2 (6.32
+# against 6.33 ms, 0.95 x when the maps arrive in NCHW; 1.07 x at 1024^2).  Off: fused=True selects the route, as for FUSED_FPN_DEFAULT.
+FUSED_THIN_DEFAULT = False
+THIN_MAX_N = 16                                            # cs_gemm_nt epilogues 10 / 11: one 16-column MFMA tile
+
+
+def _thin_rows(ops, x):
+    """x [N, C, H, W] -> its rows [N*H*W, C] for HipOps.thin_fwd: a channel-last fp32 / bf16 map (what BatchNormAct2d returns) is used in
+    place (fp32 rows are rounded to bf16 in the kernel's registers), anything else goes through _rows_bf16."""
+    N, C, H, W = x.shape
+    if x.dtype in (F32, BF16) and _is_channel_last(x) and x.data_ptr() % 16 == 0:
+        return x.permute(0, 2, 3, 1).reshape(N * H * W, C)
+    return _rows_bf16(ops, x)
+
+
+def _thin_packed(convs):
+    """(W bf16 [sum N, Cin] in module order, bias fp32 [sum N] | None) of thin convolutions that share an input.  Cached on the first
+    module, rebuilt when a parameter's version counter (or storage) changes, as in gemm_weights.  A module without a bias contributes
+    zeros when another one has a bias."""
+    key = tuple((id(c), c.weight.data_ptr(), _version(c.weight), c.weight.device,
+                 None if c.bias is None else (c.bias.data_ptr(), _version(c.bias))) for c in convs)
+    cache = convs[0].__dict__.get("_thin_cache")
+    if cache is None or cache[0] != key:
+        with torch.no_grad():
+            Wp = torch.cat([c.weight.detach().reshape(c.out_channels, c.in_channels) for c in convs]).to(BF16).contiguous()
+            if all(c.bias is None for c in convs):
+                bias = None
+            else:
+                bias = torch.cat([c.weight.new_zeros(c.out_channels) if c.bias is None else c.bias.detach() for c in convs]).to(F32).contiguous()
+        cache = convs[0].__dict__["_thin_cache"] = (key, Wp, bias)
+    return cache[1:]
+
+
+def dy_rows16(ops, grads, M):
+    """fp32 NCHW gradients [B, n_i, H, W] (contiguous) -> bf16 rows [M, 16], the modules' columns one behind the other and zeros past
+    their sum: the A operand of cs_gemm_wgrad_tn (N = 16) and of cs_colsum_bf16.  32 bytes per row beside the 512 of X."""
+    rows = ops.zeros((M, THIN_MAX_N), BF16)
+    c0 = 0
+    for g in grads:
+        B, n, H, W = g.shape
+        if B <= 65535 and W < (1 << 19):
+            ops.nchw_to_rows(g, B, H, W, n, 1, 0, rows[:, c0:])
+        else:
+            rows[:, c0:c0 + n] = g.permute(0, 2, 3, 1).reshape(M, n).to(BF16)
+        c0 += n
+    return rows
+
+
+def thin_param_grads(ops, mod, dYr, Xb, widths, need):
+    """[(dW [n_i, Cin, 1, 1] | None, db [n_i] | None)] of the modules whose columns sit in dYr bf16 [M, 16]: one cs_gemm_wgrad_tn at N = 16
+    and one cs_colsum_bf16, sliced per module.  need: [(weight?, bias?)]."""
+    Cin = Xb.shape[1]
+    dW = db = None
+    if any(w for w, _ in need):
+        dW = ops.zeros((THIN_MAX_N, Cin), F32)
+        _wgrad(ops, mod, dYr, Xb, dW)
+    if any(b for _, b in need):
+        db = ops.zeros((THIN_MAX_N,), F32)
+        ops.colsum_bf16(dYr, db)
+    out, c0 = [], 0
+    for n, (w, b) in zip(widths, need):
+        out.append((dW[c0:c0 + n].reshape(n, Cin, 1, 1) if w else None, db[c0:c0 + n] if b else None))
+        c0 += n
+    return out
+
+
+class Conv1x1Thin(nn.Conv2d):
+    """nn.Conv2d(Cin, Cout, 1) with Cout <= 16 -- its parameters, names, initialisation and state dict -- on the thin streaming kernels
+    (epilogues 10 / 11 of cs_gemm_nt) when the tensors live on a backend with THIN_HEADS and Cin % 64 == 0; F.conv2d otherwise.  The RPN's
+    rpn_cls / rpn_reg and the mask head's conv_logits.  The weight gradient is cs_gemm_wgrad_tn on dY rows padded to 16 columns, the bias
+    gradient cs_colsum_bf16: no kernel of their own.
+
+    fused: True = the kernels or NotImplementedError, False = F.conv2d, None = FUSED_THIN_DEFAULT where the kernels can run.
+    forward(x): x [N, Cin, H, W] fp32 or bf16 of any strides (a channel-last map is read in place) -> contiguous NCHW fp32
+    [N, Cout, H, W] on the kernel route, whatever x's dtype: what det_losses.rpn_loss and det_proposals.rpn_proposals take without a copy."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=1, stride=1, padding=0, bias=True, ops=None, fused=None, **kw):
+        super().__init__(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)
+        assert self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and self.dilation == (1, 1) \
+            and self.groups == 1, "Conv1x1Thin is Conv2d(kernel_size=1, stride=1, padding=0) and nothing else"
+        assert out_channels <= THIN_MAX_N, f"Conv1x1Thin has at most {THIN_MAX_N} output channels, got {out_channels} (wider: Conv1x1)"
+        self.ops = ops
+        self.fused = fused
+
+    # ------------------------------------------------------------------------------------------ dispatch
+    def covered(self, x) -> bool:
+        """What the kernels cover: fp32 parameters, a 4-D fp32 / bf16 input, Cin % 64 == 0."""
+        return (self.in_channels % 64 == 0 and self.weight.dtype == F32 and x.dim() == 4 and x.dtype in (F32, BF16)
+                and x.shape[1] == self.in_channels and x.numel() > 0 and x.device == self.weight.device)
+
+    def kernel_backend(self, x):
+        """The backend whose THIN_HEADS kernels serve forward(x), or None (-> F.conv2d); NotImplementedError where fused=True cannot be met."""
+        ops, fused = self.ops, self.fused
+        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "THIN_HEADS", False) \
+                and ops.empty((1,), F32).device == x.device:
+            k = ops if fused or FUSED_THIN_DEFAULT else None         # a host backend (the tests' reference ops) serves host tensors
+        else:
+            k = kernel_ops(x, "THIN_HEADS", ops, fused, FUSED_THIN_DEFAULT)
+        if k is not None and not self.covered(x):
+            if fused:
+                raise NotImplementedError(f"fused=True: Conv1x1Thin({self.in_channels}, {self.out_channels}) on {x.dtype} {tuple(x.shape)} is "
+                                          "outside the kernels' coverage (Cin % 64 == 0, fp32 parameters, fp32 / bf16 input)")
+            return None
+        return k
+
+    def forward(self, x):
+        k = self.kernel_backend(x)
+        if k is None:
+            return F.conv2d(x, self.weight, self.bias)
+        return _thin_apply(x, (self,), k)[0]
+
+    # ------------------------------------------------------------------------------------------ operands
+    def gemm_weights(self):
+        """(W bf16 [Cout, Cin], bias fp32 [Cout] | None), rebuilt when the parameters' version counters (or their storage) change."""
+        return _thin_packed((self,))
+
+
+def thin_heads(x, convs):
+    """[conv(x) for conv in convs] for Conv1x1Thin modules that read one input.  Two modules whose widths sum to <= 16 and whose backend
+    serves x run as ONE forward launch (the planes form of epilogue 10 with the split at the first module's width: two contiguous NCHW
+    fp32 tensors in one allocation) and ONE input-gradient launch; a missing output gradient counts as zeros.  Anything else -- a module on
+    the torch route, more than two modules, widths past 16 -- runs module by module, each by its own dispatch."""
+    convs = tuple(convs)
+    ks = [c.kernel_backend(x) for c in convs]
+    together = (len(convs) == 2 and all(k is not None and k is ks[0] for k in ks) and sum(c.out_channels for c in convs) <= THIN_MAX_N
+                and len({c.in_channels for c in convs}) == 1)
+    if not together:
+        return tuple(c(x) for c in convs)
+    return _thin_apply(x, convs, ks[0])
+
+
+def _thin_apply(x, convs, ops):
+    params = []
+    for c in convs:
+        params += [c.weight, c.bias]
+    return _ThinFn.apply(x, convs, ops, *params)
+
+
+class _ThinFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, convs, ops, *params):
+        B, Cin, H, W = x.shape
+        M, R = B * H * W, H * W
+        widths = [c.out_channels for c in convs]
+        Wp, bias = _thin_packed(convs)
+        X = _thin_rows(ops, x)
+        out = ops.empty((M * sum(widths),), F32)
+        ops.thin_fwd(X, Wp, bias, out, R=R, split=widths[0] if len(convs) == 2 else None)
+        ctx.convs, ctx.ops, ctx.geom, ctx.x_dtype, ctx.widths = convs, ops, (B, H, W), x.dtype, widths
+        if any(ctx.needs_input_grad[3:]):
+            ctx.save_for_backward(X)
+        ys, o0 = [], 0
+        for n in widths:
+            ys.append(out[o0:o0 + M * n].view(B, n, H, W))
+            o0 += M * n
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *d_outs):
+        convs, ops, widths = ctx.convs, ctx.ops, ctx.widths
+        B, H, W = ctx.geom
+        M, R, Cin = B * H * W, H * W, convs[0].in_channels
+        grads = []
+        for d, n in zip(d_outs, widths):
+            if d is None:
+                d = ops.zeros((B, n, H, W), F32)
+            grads.append(d.to(F32).contiguous())
+        dx = None
+        if ctx.needs_input_grad[0]:
+            Wp, _ = _thin_packed(convs)
+            dX = ops.empty((M, Cin), ctx.x_dtype)
+            ops.thin_dgrad(grads[0], Wp, dX, R=R, dY2=grads[1] if len(grads) == 2 else None)
+            dx = dX.view(B, H, W, Cin).permute(0, 3, 1, 2)
+        need = [(ctx.needs_input_grad[3 + 2 * i], ctx.needs_input_grad[4 + 2 * i] and c.bias is not None) for i, c in enumerate(convs)]
+        out = [None] * (2 * len(convs))
+        if any(w or b for w, b in need):
+            (X,) = ctx.saved_tensors
+            dYr = dy_rows16(ops, grads, M)
+            if X.dtype != BF16 and any(w for w, _ in need):            # an fp32 map read in place: the weight gradient's operand is bf16
+                Xc = X if X.is_contiguous() else X.contiguous()
+                Xb = ops.empty((M, Cin), BF16)
+                ops.cast_f32_bf16(Xc, Xb)
+            else:
+                Xb = X
+            for i, (dw, db) in enumerate(thin_param_grads(ops, convs[0], dYr, Xb, widths, need)):
+                out[2 * i], out[2 * i + 1] = dw, db
+        return (dx, None, None, *out)

@@ -14,7 +14,7 @@ stale() {
 }
 OBJS=""
 PIDS=""
-for f in gemm gemm_stream attention norm elementwise roialign_loss adamw preprocess det_post roi_extract det_assign det_loss det_mask det_proposal conv3x3 batchnorm runtime; do
+for f in gemm gemm_stream thin attention norm elementwise roialign_loss adamw preprocess det_post roi_extract det_assign det_loss det_mask det_proposal conv3x3 batchnorm runtime; do
   if stale "$f.hip" "_obj_$f.o"; then
     $HIPCC $FLAGS -c "$f.hip" -o "_obj_$f.o" &
     PIDS="$PIDS $!"

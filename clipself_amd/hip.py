@@ -19,6 +19,8 @@ _LIB_PATH = Path(os.environ["CLIPSELF_HIP_LIB"]) if os.environ.get("CLIPSELF_HIP
 
 EPI_BF16, EPI_F32, EPI_RESID_F32, EPI_SWIGLU_BF16, EPI_ATOMIC_F32, EPI_PATCH_F32, EPI_RESID_LN_F32, EPI_GELU_BF16, EPI_QGELU_BF16 = range(9)
 EPI_RELU_BF16 = 9                       # bf16 = ReLU(acc + bias): the detector box head's Linear + ReLU (linear.LinearAct)
+EPI_THIN_FWD, EPI_THIN_DGRAD = 10, 11   # the thin forms, N <= 16: 1 x 1 convolutions of the RPN and mask heads and their input gradient (conv.Conv1x1Thin)
+THIN_MAX_N = 16
 SPLITK_MAX, SPLITK_MIN_KTILES = 8, 16   # cs_gemm_nt's choice of `splits` for epilogues 0 / 9 (include/clipself_hip.h), restated by gemm_nt_splits
 DX_BF16, DX_F32_ASSIGN, DX_F32_ACCUM = range(3)
 ADAMW_GUARD_HEAD, ADAMW_GUARD_SPAN = 8, 16384
@@ -275,6 +277,7 @@ class HipOps:
     BATCHNORM = True                    # bn_stats / bn_finalize / bn_apply / bn_bwd_reduce / bn_bwd_apply: batch norm (+ ReLU) on channel-last rows (norm_act.BatchNormAct2d)
     LINEAR_ACT = True                   # gemm_nt(epi=EPI_RELU_BF16, splits=, extra=workspace): Linear + ReLU with deterministic split-K (linear.LinearAct)
     FPN_TOPDOWN = True                  # upsample2x_add / pool2x: the FPN's top-down add and its adjoint on channel-last rows; Conv1x1 on gemm_nt (fpn.FPN)
+    THIN_HEADS = True                   # thin_fwd / thin_dgrad: 1 x 1 convolutions with Cout <= 16 as streaming kernels, rows or NCHW planes out (conv.Conv1x1Thin, thin_heads)
     BOX_SCORES = True              # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -432,6 +435,60 @@ class HipOps:
                                  f"floats in `extra`, got {extra.dtype} with {extra.numel()} elements")
         self._ok(self.lib.cs_gemm_nt(_p(A), _p(B), _p(C), _p(bias), _p(extra), M, N, K, A.stride(0), B.stride(0),
                                      C.stride(0), epi, splits, group, flags | self.gemm_flags, self._stream()), "cs_gemm_nt")
+
+    @staticmethod
+    def _thin_form(krows, W, thin, thin2, R, split):
+        """Checks shared by thin_fwd / thin_dgrad -> (M, N, K, the `group`, the stride-or-split argument, flags) of cs_gemm_nt's thin forms
+        (include/clipself_hip.h).  krows: the K-wide rows (X / dX); thin: the N-wide side -- rows [M, N] for R == 0, else the first plane
+        block, contiguous with M * split elements; thin2: the second block (M * (N - split) elements) or None."""
+        assert krows.dim() == 2 and krows.stride(1) == 1 and krows.dtype in (torch.float32, torch.bfloat16)
+        assert W.dim() == 2 and W.stride(1) == 1 and W.dtype == torch.bfloat16 and thin.dtype == torch.float32
+        M, K = krows.shape
+        N = W.shape[0]
+        assert W.shape[1] == K and 1 <= N <= THIN_MAX_N and K % 64 == 0 and M >= 1 and krows.stride(0) >= K
+        flags = 1 if krows.dtype == torch.float32 else 0
+        if R == 0:
+            assert split is None and thin2 is None, "rows form: one [M, N] tensor, no split"
+            assert thin.dim() == 2 and tuple(thin.shape) == (M, N) and thin.stride(1) == 1 and (thin.stride(0) >= N or M == 1)
+            return M, N, K, 0, max(thin.stride(0), N), flags
+        s = N if split is None else int(split)
+        assert R >= 1 and M % R == 0 and 1 <= s <= N
+        assert thin.is_contiguous() and thin.numel() == M * s, "planes form: the first block is [M / R, s, R], contiguous"
+        if thin2 is None:
+            assert s == N, "planes form: a split below N needs the second block"
+        else:
+            assert s < N and thin2.dtype == torch.float32 and thin2.is_contiguous() and thin2.numel() == M * (N - s)
+        return M, N, K, int(R), s, flags
+
+    def thin_fwd(self, X, W, bias, out, R=0, split=None):
+        """Epilogue 10 of cs_gemm_nt: Y[m, n] = bias[n] + sum_k bf16(X[m, k]) * W[n, k], N <= 16, fp32 out.  X bf16 / fp32 rows [M, K] (row
+        stride >= K), W bf16 [N, K], bias fp32 [N] or None.  R == 0: out is rows [M, N] (row stride >= N).  R >= 1 (pixels per image, M % R
+        == 0): out is ONE contiguous fp32 allocation of M * N elements, the NCHW tensors [M / R, split, R] and [M / R, N - split, R] one
+        behind the other (split None = N: one tensor)."""
+        self._chk(X, W, bias, out)
+        if R == 0:
+            M, N, K, group, ldc, flags = self._thin_form(X, W, out, None, 0, split)
+        else:
+            assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == X.shape[0] * W.shape[0]
+            s = W.shape[0] if split is None else int(split)
+            flat = out.reshape(-1)
+            M, N, K, group, ldc, flags = self._thin_form(X, W, flat[:X.shape[0] * s], flat[X.shape[0] * s:] if s < W.shape[0] else None, R, s)
+        assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N)
+        self._ok(self.lib.cs_gemm_nt(_p(X), _p(W), _p(out), _p(bias), None, M, N, K, X.stride(0), W.stride(0), ldc, EPI_THIN_FWD, 1, group,
+                                     flags, self._stream()), "cs_gemm_nt")
+
+    def thin_dgrad(self, dY, W, dX, R=0, dY2=None, gate=None):
+        """Epilogue 11: dX[m, k] = gate(m, k) * sum_n bf16(dY[m, n]) * W[n, k].  dY fp32: rows [M, N] (R == 0), or contiguous planes
+        [M / R, s, R] with the second block dY2 [M / R, N - s, R] (s = dY.numel() / M; None: s == N).  dX bf16 / fp32 rows [M, K] (row stride >=
+        K), written whole.  gate: bf16 rows [M, K] with dX's row stride; where gate <= 0, dX = 0 (a NaN gate passes)."""
+        self._chk(dY, W, dX, dY2, gate)
+        split = None if R == 0 else dY.numel() // dX.shape[0]
+        M, N, K, group, lda, flags = self._thin_form(dX, W, dY, dY2, R, split)
+        if gate is not None:
+            assert gate.dtype == torch.bfloat16 and tuple(gate.shape) == (M, K) and gate.stride(1) == 1 and (gate.stride(0) == dX.stride(0) or M == 1), \
+                "the gate is bf16 rows [M, K] with dX's row stride"
+        self._ok(self.lib.cs_gemm_nt(_p(dY), _p(W), _p(dX), _p(dY2), _p(gate), M, N, K, lda, W.stride(0), dX.stride(0), EPI_THIN_DGRAD, 1, group,
+                                     flags, self._stream()), "cs_gemm_nt")
 
     def gemm_nt_splits(self, M, N, K) -> int:
         """The slice count cs_gemm_nt chooses for splits <= 0 on epilogues 0 / 9 (the rule of include/clipself_hip.h): what a caller sizes the

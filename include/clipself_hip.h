@@ -34,6 +34,8 @@ const char* cs_last_error(void);
  *        (src/open_clip/transformer.py:209-213 `mlp`, :31-34 `QuickGELU`) |
  *      9 bf16 = ReLU(acc+bias), v < 0 ? 0 : v (a NaN passes): the detector box head's Linear + ReLU
  *        (F-ViT/models/fvit_head.py:82-83, 95-96, 104-105: shared_fcs, cls_fcs, reg_fcs)
+ *      10 / 11 the THIN forms: 1 <= N <= 16 output columns, a stream over the rows and not a tiled GEMM (see below; their own argument
+ *        rules replace the ones of this paragraph)
  * splits: 1 everywhere except
  *      epi 4: the atomic split-K above;
  *      epi 0 / 9: deterministic split-K for skinny, deep problems (the box head's 4096 x 512 outputs behind K = 12 544).  `splits` > 1, or
@@ -48,7 +50,36 @@ const char* cs_last_error(void);
  *        splits != 1 on any other epilogue (or on cs_gemm_nt_ln's folded LayerNorm).
  * flags bit0: use register staging instead of the global_load_lds DMA path; bits 4-7: force a tile schedule (0 = heuristic; 11 = the
  * streaming persistent kernel with register-level epilogues, the default for the bf16 / QuickGELU / SwiGLU epilogues of large problems);
- * bits 20-27: compute units the persistent kernels leave free (0 = use all 256; data-parallel runs reserve a few for RCCL's kernels). */
+ * bits 20-27: compute units the persistent kernels leave free (0 = use all 256; data-parallel runs reserve a few for RCCL's kernels).
+ *
+ * THIN FORMS, epi 10 / 11: 1 x 1 convolutions with at most 16 output channels on channel-last rows -- the RPN's rpn_cls | rpn_reg
+ * (F-ViT/models/custom_rpn_head.py, mmdet RPNHead: 256 -> 3 and 256 -> 12, one launch for both) and the mask head's conv_logits (mmdet
+ * FCNMaskHead: 256 -> 1) -- and their input gradient.  1 <= N <= 16, K % 64 == 0, W = B is bf16 [N, K] (ldb % 8 == 0, 16-byte aligned),
+ * splits == 1, flags bit 0 = the K-wide rows (X of epi 10, dX of epi 11) are fp32 instead of bf16; the other flag bits are ignored.
+ * M rows are pixels in (image, y, x) order.  `group` selects how the N-wide side is laid out:
+ *   group == 0, ROWS:   T[m * ld + n], n < N; columns >= N of a row are never touched.
+ *   group == R >= 1, PLANES: M % R == 0 (R = h * w pixels per image) and a split s, 1 <= s <= N.  Column n < s of row m is element
+ *                       P1[((m / R) * s + n) * R + m % R], column n >= s is P2[((m / R) * (N - s) + (n - s)) * R + m % R]: two contiguous
+ *                       NCHW fp32 tensors [M / R, s, h, w] and [M / R, N - s, h, w]; s == N leaves one tensor and P2 unused.
+ *   epi 10, forward:  Y[m, n] = bias[n] + sum_k bf16(X[m, k]) * W[n, k].
+ *       A = X rows [M, K], bf16 or fp32 (flags bit 0), row stride lda >= K with 16-byte aligned rows (lda % 8 == 0 / lda % 4 == 0); fp32
+ *       values are rounded to bf16 (to nearest even) in registers, so the bits equal cs_cast_f32_bf16 followed by the bf16 form.
+ *       bias fp32 [N] or NULL.  fp32 accumulation; the output is fp32, acc + bias, not rounded again.
+ *       C = Y: rows form T = C with ld = ldc >= N; planes form P1 = C, P2 = C + M * s (ONE allocation of M * N floats) and ldc = s.
+ *       Planes are stored 16 bytes (four pixels) at a time where R % 4 == 0 and C is 16-byte aligned, one element per lane otherwise
+ *       (any R >= 1).  `extra` is not read.
+ *   epi 11, input gradient:  dX[m, k] = gate(m, k) * sum_n bf16(dY[m, n]) * W[n, k].
+ *       A = dY, fp32: rows form T = A with ld = lda >= N; planes form P1 = A, P2 = bias (the two gradients autograd hands are separate
+ *       allocations; NULL requires s == N) and lda = s.  dY is rounded to bf16 in registers (operands bf16, accumulation fp32).
+ *       C = dX rows [M, K], bf16 or fp32 (flags bit 0), row stride ldc >= K with 16-byte aligned rows; rounded once, at its type.
+ *       extra = gate, or NULL: bf16 rows [M, K] with dX's row stride ldc, 16-byte aligned.  Where gate <= 0, dX = 0 (a NaN gate passes,
+ *       the ReLU rule of epi 9): the ReLU between the mask head's transposed convolution and conv_logits, for the gate's read alone.
+ *   Both: plain vector loads and stores, no atomics, no workspace; every output element is written exactly once per call and nothing
+ *   outside the stated extents is touched; 64-bit offsets; a wave owns 16 rows at a time on one v_mfma_f32_16x16x32_bf16 tile (the weights
+ *   stay in registers for the whole launch when K == 256) and the grid is min(ceil(M / 64), 8 * compute units) workgroups of 256 threads
+ *   with a grid-stride loop: a function of the arguments and the device alone.  Equal inputs give equal bits.
+ *   Errors (-1, cs_last_error, nothing launched): N > 16, K % 64 != 0, M % R != 0, s outside [1, N], a stride below its width or one that
+ *   breaks the 16-byte rows, misaligned bases, a second block with s == N or none with s < N (epi 11), splits != 1. */
 int cs_gemm_nt(const void* A, const void* B, void* C, const float* bias, const float* extra, int M, int N, int K,
                int lda, int ldb, int ldc, int epi, int splits, int group, int flags, cs_stream_t stream);
 
