@@ -28,7 +28,7 @@ class ConvFCBBoxHead(nn.Module):
     """ConvFCBBoxHead(**the config's bbox_head dict).  forward(x [K, in_channels, s, s]) -> (x_cls [K, fc_out_channels], bbox_pred [K, 4 |
     4 * num_classes]): fvit_head.py:72-107 up to the class branch's output, which goes to OpenVocabBoxScores.class_logits unchanged.
 
-    ops / fused are handed to every kernel-backed submodule (see conv.Conv3x3.fused)."""
+    ops / fused are handed to every kernel-backed submodule (see det_layer.KernelLayer)."""
 
     def __init__(self, in_channels=256, fc_out_channels=1024, roi_feat_size=7, num_shared_convs=0, num_shared_fcs=0, num_cls_convs=0,
                  num_cls_fcs=0, num_reg_convs=0, num_reg_fcs=0, conv_out_channels=256, num_classes=80, reg_class_agnostic=False,

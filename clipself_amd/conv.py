@@ -16,10 +16,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .det_backend import kernel_ops
-from .neck import CHUNK_BYTES, EPI_BF16, EPI_F32, _version, _wgrad
-
-BF16, F32 = torch.bfloat16, torch.float32
+from .det_layer import (BF16, F32, KernelLayer, bias_f32, conv_covered, epi_for, is_channel_last, kernel_grad, packed, pad_cols, params_key,
+                        row_chunks, rows_bf16, rows_to_map, wgrad)
 
 # Whether fused=None takes the kernels where the backend has them: set from profiles/conv3x3_bench.md by the rule of FUSED_SCORES_DEFAULT
 # and FUSED_PROPOSALS_DEFAULT -- on only if the kernel route wins forward + backward against the faster torch variant at all four shapes.
@@ -39,35 +37,31 @@ def pack_weights(weight):
 
 
 def _pad_k(Wm):
-    """A packed weight matrix with K = 9*C padded with zero columns to a multiple of 64 (cs_gemm_nt's K tile): the im2col route of a
-    channel count that is no multiple of 64."""
-    K = Wm.shape[1]
-    Kp = (K + 63) // 64 * 64
-    if Kp == K:
-        return Wm
-    out = Wm.new_zeros(Wm.shape[0], Kp)
-    out[:, :K] = Wm
-    return out
+    """det_layer.pad_cols of a packed weight matrix under the name it had here, for callers written before it moved."""
+    return pad_cols(None, Wm)
 
 
-def _is_channel_last(t):
-    """True when t [N, C, H, W] is dense in (n, y, x, c) order, so that its rows [N*H*W, C] are a view."""
-    return t.permute(0, 2, 3, 1).is_contiguous()
+class _ConvLayer(KernelLayer, nn.Conv2d):
+    """What the three convolutions share of their dispatch: the coverage predicate and the name in the refusal."""
+    COUT_MULTIPLE = 8
+    COVERAGE = "Cin % 64 == 0, Cout % 8 == 0, fp32 parameters, fp32 / bf16 input"
+
+    def covered(self, x) -> bool:
+        """What the kernels cover: fp32 parameters, a 4-D fp32 / bf16 input, Cin % 64 == 0, Cout % COUT_MULTIPLE == 0."""
+        return conv_covered(self, x, self.COUT_MULTIPLE)
+
+    def describe(self):
+        return f"{type(self).__name__}({self.in_channels}, {self.out_channels})"
 
 
-def _row_chunks(M, row_bytes):
-    """[(row0, rows)] covering M rows with chunks of at most CHUNK_BYTES (neck._chunks, on rows instead of images)."""
-    n = max(1, min(M, CHUNK_BYTES // max(1, row_bytes)))
-    return [(r0, min(n, M - r0)) for r0 in range(0, M, n)]
-
-
-class Conv3x3(nn.Conv2d):
+class Conv3x3(_ConvLayer):
     """nn.Conv2d(Cin, Cout, 3, padding=1) -- its parameters, names, initialisation and state dict -- whose forward and backward run on the
     HIP kernels when the tensors live on a backend with CONV3X3, Cin % 64 == 0 and Cout % 8 == 0; F.conv2d otherwise.
 
     fused: True = the kernels or NotImplementedError, False = F.conv2d, None = FUSED_CONV_DEFAULT where the kernels can run.
     route: "implicit" (csc_conv3x3) or "im2col" (csc_im2col3x3 + cs_gemm_nt) for the forward and the input gradient.
     forward(x): x [N, Cin, H, W] fp32 or bf16 of any strides -> [N, Cout, H, W] of x's dtype with channel-last strides (kernel route)."""
+    FLAG = "CONV3X3"
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True, ops=None, fused=None, route="implicit", **kw):
         super().__init__(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)
@@ -77,28 +71,9 @@ class Conv3x3(nn.Conv2d):
         self.ops = ops
         self.fused = fused
         self.route = route
-        self._wcache = None
 
-    # ------------------------------------------------------------------------------------------ dispatch
-    def covered(self, x) -> bool:
-        """What the kernels cover: fp32 parameters, a 4-D fp32 / bf16 input, Cin % 64 == 0, Cout % 8 == 0."""
-        return (self.in_channels % 64 == 0 and self.out_channels % 8 == 0 and self.weight.dtype == F32 and x.dim() == 4
-                and x.dtype in (F32, BF16) and x.shape[1] == self.in_channels and x.numel() > 0 and x.device == self.weight.device)
-
-    def kernel_backend(self, x):
-        """The backend whose CONV3X3 kernels serve forward(x), or None (-> F.conv2d); NotImplementedError where fused=True cannot be met."""
-        ops, fused = self.ops, self.fused
-        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "CONV3X3", False) \
-                and ops.empty((1,), F32).device == x.device:
-            k = ops if fused or FUSED_CONV_DEFAULT else None          # a host backend (the tests' reference ops) serves host tensors
-        else:
-            k = kernel_ops(x, "CONV3X3", ops, fused, FUSED_CONV_DEFAULT)
-        if k is not None and not self.covered(x):
-            if fused:
-                raise NotImplementedError(f"fused=True: Conv3x3({self.in_channels}, {self.out_channels}) on {x.dtype} {tuple(x.shape)} is outside "
-                                          "the kernels' coverage (Cin % 64 == 0, Cout % 8 == 0, fp32 parameters, fp32 / bf16 input)")
-            return None
-        return k
+    def fused_default(self):
+        return FUSED_CONV_DEFAULT
 
     def forward(self, x):
         k = self.kernel_backend(x)
@@ -110,32 +85,7 @@ class Conv3x3(nn.Conv2d):
     def gemm_weights(self):
         """(Wg bf16 [Cout, 9*Cin], WgT bf16 [Cin, 9*Cout], bias fp32 [Cout] | None), see pack_weights.  Rebuilt when the parameters'
         version counters (or their storage) change."""
-        w, b = self.weight, self.bias
-        key = (w.data_ptr(), _version(w), w.device, None if b is None else (b.data_ptr(), _version(b)))
-        if self._wcache is None or self._wcache[0] != key:
-            with torch.no_grad():
-                Wg, WgT = pack_weights(w)
-                bias = None if b is None else b.detach().to(F32).contiguous()
-            self._wcache = (key, Wg, WgT, bias)
-        return self._wcache[1:]
-
-
-def _rows_bf16(ops, t):
-    """t [N, C, H, W] fp32 / bf16 of any strides -> bf16 rows [N*H*W, C].  A channel-last bf16 tensor is returned as a view; a channel-last
-    fp32 one goes through the cast kernel; a contiguous NCHW one through nchw_to_rows (cast and permutation in one pass)."""
-    N, C, H, W = t.shape
-    if not _is_channel_last(t) and not t.is_contiguous():
-        t = t.contiguous(memory_format=torch.channels_last)
-    if _is_channel_last(t):
-        rows = t.permute(0, 2, 3, 1).reshape(N * H * W, C)
-        if t.dtype == BF16:
-            return rows
-        out = ops.empty((N * H * W, C), BF16)
-        ops.cast_f32_bf16(rows, out)
-        return out
-    out = ops.empty((N * H * W, C), BF16)
-    ops.nchw_to_rows(t, N, H, W, C, 1, 0, out)
-    return out
+        return packed(self, lambda: (*pack_weights(self.weight), bias_f32(self.bias)))
 
 
 def _conv_rows(ops, route, X, Wm, bias, out, N, H, W):
@@ -144,11 +94,11 @@ def _conv_rows(ops, route, X, Wm, bias, out, N, H, W):
     if route == "implicit" and Ci % 64 == 0:
         ops.conv3x3(X, Wm, out, bias, N, H, W)
         return
-    Wp = _pad_k(Wm)
+    Wp = pad_cols(ops, Wm)                                 # K = 9*Ci up to cs_gemm_nt's K tile: a channel count that is no multiple of 64
     Kp = Wp.shape[1]
-    epi = EPI_F32 if out.dtype == F32 else EPI_BF16
+    epi = epi_for(out.dtype)
     cols = None
-    for r0, n in _row_chunks(M, Kp * 2):
+    for r0, n in row_chunks(M, Kp * 2):
         if cols is None or cols.shape[0] != n:
             cols = ops.empty((n, Kp), BF16) if Kp == 9 * Ci else ops.zeros((n, Kp), BF16)     # the K padding stays zero: im2col never writes it
         ops.im2col3x3(X, cols[:, :9 * Ci], N, H, W, r0)
@@ -161,14 +111,14 @@ class _Conv3x3Fn(torch.autograd.Function):
         N, Cin, H, W = x.shape
         Cout = mod.out_channels
         Wg, _, b32 = mod.gemm_weights()
-        X = _rows_bf16(ops, x)
+        X = rows_bf16(ops, x)
         Y = ops.empty((N * H * W, Cout), x.dtype)
         _conv_rows(ops, route, X, Wg, b32, Y, N, H, W)
         ctx.mod, ctx.ops, ctx.route, ctx.geom, ctx.x_dtype = mod, ops, route, (N, H, W), x.dtype
         ctx.has_bias = bias is not None
         if any(ctx.needs_input_grad[1:3]):
             ctx.save_for_backward(X)                       # the bf16 map, not the nine times larger matrix
-        return Y.view(N, H, W, Cout).permute(0, 3, 1, 2)
+        return rows_to_map(Y, N, H, W)
 
     @staticmethod
     def backward(ctx, d_out):
@@ -176,24 +126,22 @@ class _Conv3x3Fn(torch.autograd.Function):
         N, H, W = ctx.geom
         Cin, Cout, M = mod.in_channels, mod.out_channels, N * H * W
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
-        if d_out.dtype not in (F32, BF16):
-            d_out = d_out.to(F32)
-        dY = _rows_bf16(ops, d_out)
+        dY = rows_bf16(ops, kernel_grad(d_out))
         dx = dw = db = None
         if need_x:
             _, WgT, _ = mod.gemm_weights()
             dX = ops.empty((M, Cin), ctx.x_dtype)
             _conv_rows(ops, route, dY, WgT, None, dX, N, H, W)
-            dx = dX.view(N, H, W, Cin).permute(0, 3, 1, 2)
+            dx = rows_to_map(dX, N, H, W)
         if need_w:
             (X,) = ctx.saved_tensors
             dWg = ops.zeros((Cout, 9 * Cin), F32)
             cols = None
-            for r0, n in _row_chunks(M, 9 * Cin * 2):
+            for r0, n in row_chunks(M, 9 * Cin * 2):
                 if cols is None or cols.shape[0] != n:
                     cols = ops.empty((n, 9 * Cin), BF16)
                 ops.im2col3x3(X, cols, N, H, W, r0)
-                _wgrad(ops, mod, dY[r0:r0 + n], cols, dWg)
+                wgrad(ops, mod, dY[r0:r0 + n], cols, dWg)
             dw = dWg.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
         if need_b:
             db = ops.zeros((Cout,), F32)
@@ -220,7 +168,7 @@ def pack_weights_1x1(weight):
     return Wm, WT
 
 
-class Conv1x1(nn.Conv2d):
+class Conv1x1(_ConvLayer):
     """nn.Conv2d(Cin, Cout, 1) -- its parameters, names, initialisation and state dict -- as one GEMM on channel-last rows,
     Y[N*H*W, Cout] = X[N*H*W, Cin] . W^T + bias, when the tensors live on a backend with FPN_TOPDOWN, Cin % 64 == 0 and Cout % 8 == 0 (what
     cs_gemm_nt and cs_gemm_wgrad_tn take); F.conv2d otherwise.  No kernel of its own: cs_gemm_nt forward and for the input gradient,
@@ -228,6 +176,7 @@ class Conv1x1(nn.Conv2d):
 
     fused: True = the kernels or NotImplementedError, False = F.conv2d, None = FUSED_CONV1X1_DEFAULT where the kernels can run.
     forward(x): x [N, Cin, H, W] fp32 or bf16 of any strides -> [N, Cout, H, W] of x's dtype with channel-last strides (kernel route)."""
+    FLAG = "FPN_TOPDOWN"                                   # the backend that has the top-down kernels has the laterals' GEMMs
 
     def __init__(self, in_channels, out_channels, kernel_size=1, stride=1, padding=0, bias=True, ops=None, fused=None, **kw):
         super().__init__(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)
@@ -235,28 +184,9 @@ class Conv1x1(nn.Conv2d):
             and self.groups == 1, "Conv1x1 is Conv2d(kernel_size=1, stride=1, padding=0) and nothing else"
         self.ops = ops
         self.fused = fused
-        self._wcache = None
 
-    # ------------------------------------------------------------------------------------------ dispatch
-    def covered(self, x) -> bool:
-        """What the kernels cover: fp32 parameters, a 4-D fp32 / bf16 input, Cin % 64 == 0, Cout % 8 == 0."""
-        return (self.in_channels % 64 == 0 and self.out_channels % 8 == 0 and self.weight.dtype == F32 and x.dim() == 4
-                and x.dtype in (F32, BF16) and x.shape[1] == self.in_channels and x.numel() > 0 and x.device == self.weight.device)
-
-    def kernel_backend(self, x):
-        """The backend whose GEMMs serve forward(x), or None (-> F.conv2d); NotImplementedError where fused=True cannot be met."""
-        ops, fused = self.ops, self.fused
-        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "FPN_TOPDOWN", False) \
-                and ops.empty((1,), F32).device == x.device:
-            k = ops if fused or FUSED_CONV1X1_DEFAULT else None       # a host backend (the tests' reference ops) serves host tensors
-        else:
-            k = kernel_ops(x, "FPN_TOPDOWN", ops, fused, FUSED_CONV1X1_DEFAULT)
-        if k is not None and not self.covered(x):
-            if fused:
-                raise NotImplementedError(f"fused=True: Conv1x1({self.in_channels}, {self.out_channels}) on {x.dtype} {tuple(x.shape)} is outside "
-                                          "the kernels' coverage (Cin % 64 == 0, Cout % 8 == 0, fp32 parameters, fp32 / bf16 input)")
-            return None
-        return k
+    def fused_default(self):
+        return FUSED_CONV1X1_DEFAULT
 
     def forward(self, x):
         k = self.kernel_backend(x)
@@ -268,14 +198,7 @@ class Conv1x1(nn.Conv2d):
     def gemm_weights(self):
         """(W bf16 [Cout, Cin], WT bf16 [Cin, Cout rounded up to 64], bias fp32 [Cout] | None), see pack_weights_1x1.  Rebuilt when the
         parameters' version counters (or their storage) change."""
-        w, b = self.weight, self.bias
-        key = (w.data_ptr(), _version(w), w.device, None if b is None else (b.data_ptr(), _version(b)))
-        if self._wcache is None or self._wcache[0] != key:
-            with torch.no_grad():
-                Wm, WT = pack_weights_1x1(w)
-                bias = None if b is None else b.detach().to(F32).contiguous()
-            self._wcache = (key, Wm, WT, bias)
-        return self._wcache[1:]
+        return packed(self, lambda: (*pack_weights_1x1(self.weight), bias_f32(self.bias)))
 
 
 class _Conv1x1Fn(torch.autograd.Function):
@@ -284,14 +207,14 @@ class _Conv1x1Fn(torch.autograd.Function):
         N, Cin, H, W = x.shape
         Cout = mod.out_channels
         Wm, _, b32 = mod.gemm_weights()
-        X = _rows_bf16(ops, x)
+        X = rows_bf16(ops, x)
         Y = ops.empty((N * H * W, Cout), x.dtype)
-        ops.gemm_nt(X, Wm, Y, b32, epi=EPI_F32 if x.dtype == F32 else EPI_BF16)
+        ops.gemm_nt(X, Wm, Y, b32, epi=epi_for(x.dtype))
         ctx.mod, ctx.ops, ctx.geom, ctx.x_dtype = mod, ops, (N, H, W), x.dtype
         ctx.has_bias = bias is not None
         if ctx.needs_input_grad[1]:
             ctx.save_for_backward(X)
-        return Y.view(N, H, W, Cout).permute(0, 3, 1, 2)
+        return rows_to_map(Y, N, H, W)
 
     @staticmethod
     def backward(ctx, d_out):
@@ -299,25 +222,18 @@ class _Conv1x1Fn(torch.autograd.Function):
         N, H, W = ctx.geom
         Cin, Cout, M = mod.in_channels, mod.out_channels, N * H * W
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
-        if d_out.dtype not in (F32, BF16):
-            d_out = d_out.to(F32)
-        dY = _rows_bf16(ops, d_out)
+        dY = rows_bf16(ops, kernel_grad(d_out))
         dx = dw = db = None
         if need_x:
             _, WT, _ = mod.gemm_weights()
-            Kp = WT.shape[1]
-            if Kp != Cout:                                             # zero columns pad the contraction to the K tile
-                dYp = ops.zeros((M, Kp), BF16)
-                dYp[:, :Cout] = dY
-            else:
-                dYp = dY
+            dYp = pad_cols(ops, dY)                                    # zero columns pad the contraction to WT's K tile
             dX = ops.empty((M, Cin), ctx.x_dtype)
-            ops.gemm_nt(dYp, WT, dX, None, epi=EPI_F32 if ctx.x_dtype == F32 else EPI_BF16)
-            dx = dX.view(N, H, W, Cin).permute(0, 3, 1, 2)
+            ops.gemm_nt(dYp, WT, dX, None, epi=epi_for(ctx.x_dtype))
+            dx = rows_to_map(dX, N, H, W)
         if need_w:
             (X,) = ctx.saved_tensors
             dWm = ops.zeros((Cout, Cin), F32)
-            _wgrad(ops, mod, dY, X, dWm)
+            wgrad(ops, mod, dY, X, dWm)
             dw = dWm.view(Cout, Cin, 1, 1)
         if need_b:
             db = ops.zeros((Cout,), F32)
@@ -337,29 +253,23 @@ THIN_MAX_N = 16                                            # cs_gemm_nt epilogue
 
 def _thin_rows(ops, x):
     """x [N, C, H, W] -> its rows [N*H*W, C] for HipOps.thin_fwd: a channel-last fp32 / bf16 map (what BatchNormAct2d returns) is used in
-    place (fp32 rows are rounded to bf16 in the kernel's registers), anything else goes through _rows_bf16."""
+    place (fp32 rows are rounded to bf16 in the kernel's registers), anything else goes through rows_bf16."""
     N, C, H, W = x.shape
-    if x.dtype in (F32, BF16) and _is_channel_last(x) and x.data_ptr() % 16 == 0:
+    if x.dtype in (F32, BF16) and is_channel_last(x) and x.data_ptr() % 16 == 0:
         return x.permute(0, 2, 3, 1).reshape(N * H * W, C)
-    return _rows_bf16(ops, x)
+    return rows_bf16(ops, x)
 
 
 def _thin_packed(convs):
     """(W bf16 [sum N, Cin] in module order, bias fp32 [sum N] | None) of thin convolutions that share an input.  Cached on the first
     module, rebuilt when a parameter's version counter (or storage) changes, as in gemm_weights.  A module without a bias contributes
     zeros when another one has a bias."""
-    key = tuple((id(c), c.weight.data_ptr(), _version(c.weight), c.weight.device,
-                 None if c.bias is None else (c.bias.data_ptr(), _version(c.bias))) for c in convs)
-    cache = convs[0].__dict__.get("_thin_cache")
-    if cache is None or cache[0] != key:
-        with torch.no_grad():
-            Wp = torch.cat([c.weight.detach().reshape(c.out_channels, c.in_channels) for c in convs]).to(BF16).contiguous()
-            if all(c.bias is None for c in convs):
-                bias = None
-            else:
-                bias = torch.cat([c.weight.new_zeros(c.out_channels) if c.bias is None else c.bias.detach() for c in convs]).to(F32).contiguous()
-        cache = convs[0].__dict__["_thin_cache"] = (key, Wp, bias)
-    return cache[1:]
+    def build():
+        Wp = torch.cat([c.weight.detach().reshape(c.out_channels, c.in_channels) for c in convs]).to(BF16).contiguous()
+        if all(c.bias is None for c in convs):
+            return Wp, None
+        return Wp, torch.cat([c.weight.new_zeros(c.out_channels) if c.bias is None else c.bias.detach() for c in convs]).to(F32).contiguous()
+    return packed(convs[0], build, key=tuple((id(c), *params_key(c.weight, c.bias)) for c in convs), slot="_thin_cache")
 
 
 def dy_rows16(ops, grads, M):
@@ -384,7 +294,7 @@ def thin_param_grads(ops, mod, dYr, Xb, widths, need):
     dW = db = None
     if any(w for w, _ in need):
         dW = ops.zeros((THIN_MAX_N, Cin), F32)
-        _wgrad(ops, mod, dYr, Xb, dW)
+        wgrad(ops, mod, dYr, Xb, dW)
     if any(b for _, b in need):
         db = ops.zeros((THIN_MAX_N,), F32)
         ops.colsum_bf16(dYr, db)
@@ -395,7 +305,7 @@ def thin_param_grads(ops, mod, dYr, Xb, widths, need):
     return out
 
 
-class Conv1x1Thin(nn.Conv2d):
+class Conv1x1Thin(_ConvLayer):
     """nn.Conv2d(Cin, Cout, 1) with Cout <= 16 -- its parameters, names, initialisation and state dict -- on the thin streaming kernels
     (epilogues 10 / 11 of cs_gemm_nt) when the tensors live on a backend with THIN_HEADS and Cin % 64 == 0; F.conv2d otherwise.  The RPN's
     rpn_cls / rpn_reg and the mask head's conv_logits.  The weight gradient is cs_gemm_wgrad_tn on dY rows padded to 16 columns, the bias
@@ -404,6 +314,8 @@ class Conv1x1Thin(nn.Conv2d):
     fused: True = the kernels or NotImplementedError, False = F.conv2d, None = FUSED_THIN_DEFAULT where the kernels can run.
     forward(x): x [N, Cin, H, W] fp32 or bf16 of any strides (a channel-last map is read in place) -> contiguous NCHW fp32
     [N, Cout, H, W] on the kernel route, whatever x's dtype: what det_losses.rpn_loss and det_proposals.rpn_proposals take without a copy."""
+    FLAG, COUT_MULTIPLE = "THIN_HEADS", 1                  # any Cout <= THIN_MAX_N
+    COVERAGE = "Cin % 64 == 0, fp32 parameters, fp32 / bf16 input"
 
     def __init__(self, in_channels, out_channels, kernel_size=1, stride=1, padding=0, bias=True, ops=None, fused=None, **kw):
         super().__init__(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)
@@ -413,26 +325,8 @@ class Conv1x1Thin(nn.Conv2d):
         self.ops = ops
         self.fused = fused
 
-    # ------------------------------------------------------------------------------------------ dispatch
-    def covered(self, x) -> bool:
-        """What the kernels cover: fp32 parameters, a 4-D fp32 / bf16 input, Cin % 64 == 0."""
-        return (self.in_channels % 64 == 0 and self.weight.dtype == F32 and x.dim() == 4 and x.dtype in (F32, BF16)
-                and x.shape[1] == self.in_channels and x.numel() > 0 and x.device == self.weight.device)
-
-    def kernel_backend(self, x):
-        """The backend whose THIN_HEADS kernels serve forward(x), or None (-> F.conv2d); NotImplementedError where fused=True cannot be met."""
-        ops, fused = self.ops, self.fused
-        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "THIN_HEADS", False) \
-                and ops.empty((1,), F32).device == x.device:
-            k = ops if fused or FUSED_THIN_DEFAULT else None         # a host backend (the tests' reference ops) serves host tensors
-        else:
-            k = kernel_ops(x, "THIN_HEADS", ops, fused, FUSED_THIN_DEFAULT)
-        if k is not None and not self.covered(x):
-            if fused:
-                raise NotImplementedError(f"fused=True: Conv1x1Thin({self.in_channels}, {self.out_channels}) on {x.dtype} {tuple(x.shape)} is "
-                                          "outside the kernels' coverage (Cin % 64 == 0, fp32 parameters, fp32 / bf16 input)")
-            return None
-        return k
+    def fused_default(self):
+        return FUSED_THIN_DEFAULT
 
     def forward(self, x):
         k = self.kernel_backend(x)
@@ -501,7 +395,7 @@ class _ThinFn(torch.autograd.Function):
             Wp, _ = _thin_packed(convs)
             dX = ops.empty((M, Cin), ctx.x_dtype)
             ops.thin_dgrad(grads[0], Wp, dX, R=R, dY2=grads[1] if len(grads) == 2 else None)
-            dx = dX.view(B, H, W, Cin).permute(0, 3, 1, 2)
+            dx = rows_to_map(dX, B, H, W)
         need = [(ctx.needs_input_grad[3 + 2 * i], ctx.needs_input_grad[4 + 2 * i] and c.bias is not None) for i, c in enumerate(convs)]
         out = [None] * (2 * len(convs))
         if any(w or b for w, b in need):

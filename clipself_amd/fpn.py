@@ -20,11 +20,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .det_backend import kernel_ops
-from .norm_act import ConvModule, _rows
-
-BF16, F32 = torch.bfloat16, torch.float32
-NORMS = ("BN", "SyncBN", "MMSyncBN")          # what build_norm_layer abbreviates to `bn`: all of them are BatchNormAct2d here
+from .det_layer import BF16, F32, channel_last_rows, kernel_grad, layer_ops, rows_to_map, uncovered
+from .norm_act import NORMS, ConvModule, apply_norm_cfg  # noqa: F401  (NORMS stays importable from here)
 
 # Whether fused=None takes the top-down kernels where the backend has them: set from profiles/fpn_bench.md by the rule of
 # conv.FUSED_CONV_DEFAULT -- on only if the kernel route wins forward + backward against the faster torch variant at every measured shape.
@@ -45,7 +42,7 @@ def _topdown_covered(fine, coarse) -> bool:
             and coarse.numel() > 0)
 
 
-class _TopDownFn(torch.autograd.Function):
+class TopDownFn(torch.autograd.Function):
     """fine + nearest_up2(coarse) on the kernels.  forward: form 7 accumulates into one channel-last copy of `fine`.  The laterals' maps are
     views that _BatchNormActFn / _Conv1x1Fn create inside a custom Function, and autograd refuses an in-place write (mark_dirty) on such a
     view -- it could not rebase their backward -- so the copy it asks for is taken here; its cost is part of every figure in
@@ -56,7 +53,7 @@ class _TopDownFn(torch.autograd.Function):
         B, C, h, w = coarse.shape
         out = ops.empty((B, 2 * h, 2 * w, C), fine.dtype)
         out.copy_(fine.permute(0, 2, 3, 1))                            # channel-last whatever fine's strides were
-        ops.upsample2x_add(_rows(coarse), out.view(4 * B * h * w, C), B, h, w, C, accumulate=True)
+        ops.upsample2x_add(channel_last_rows(coarse), out.view(4 * B * h * w, C), B, h, w, C, accumulate=True)
         ctx.ops, ctx.geom, ctx.coarse_dtype = ops, (B, h, w, C), coarse.dtype
         return out.permute(0, 3, 1, 2)
 
@@ -66,11 +63,10 @@ class _TopDownFn(torch.autograd.Function):
         B, h, w, C = ctx.geom
         d_coarse = None
         if ctx.needs_input_grad[1]:
-            if g.dtype not in (F32, BF16):
-                g = g.to(F32)
+            g = kernel_grad(g)
             dC = ops.empty((B * h * w, C), ctx.coarse_dtype)
-            ops.pool2x(_rows(g), dC, B, h, w, C, accumulate=False)
-            d_coarse = dC.view(B, h, w, C).permute(0, 3, 1, 2)
+            ops.pool2x(channel_last_rows(g), dC, B, h, w, C, accumulate=False)
+            d_coarse = rows_to_map(dC, B, h, w)
         return (g if ctx.needs_input_grad[0] else None), d_coarse, None
 
 
@@ -99,8 +95,6 @@ class FPN(nn.Module):
         for name, (got, only) in options.items():
             if got != only:
                 raise NotImplementedError(f"FPN: {name}={got!r} is not built here (only {name}={only!r}, what the F-ViT configs use)")
-        if norm_cfg is not None and norm_cfg.get("type") not in NORMS:
-            raise NotImplementedError(f"FPN: norm_cfg={norm_cfg!r} is not built here (type one of {NORMS}, or norm_cfg=None)")
         assert num_outs >= len(in_channels), "num_outs counts the extra levels on top of the len(in_channels) pyramid levels"
         self.in_channels = list(in_channels)
         self.out_channels = out_channels
@@ -116,25 +110,15 @@ class FPN(nn.Module):
                 nn.init.xavier_uniform_(m.weight, gain=1)
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
-        if norm and not norm_cfg.get("requires_grad", True):           # build_norm_layer: param.requires_grad = requires_grad
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.requires_grad_(False)
+        apply_norm_cfg(self, norm_cfg)
 
     # ------------------------------------------------------------------------------------------ the top-down step
     def _topdown_backend(self, fine, coarse):
         """The backend whose FPN_TOPDOWN kernels add `coarse` into `fine`, or None (-> torch); NotImplementedError where fused=True cannot be met."""
-        ops, fused = self.ops, self.fused
-        if fused is not False and ops is not None and not fine.is_cuda and getattr(ops, "FPN_TOPDOWN", False) \
-                and ops.empty((1,), F32).device == fine.device:
-            k = ops if fused or FUSED_FPN_DEFAULT else None            # a host backend (the tests' reference ops) serves host tensors
-        else:
-            k = kernel_ops(fine, "FPN_TOPDOWN", ops, fused, FUSED_FPN_DEFAULT)
+        k = layer_ops(fine, "FPN_TOPDOWN", self.ops, self.fused, FUSED_FPN_DEFAULT)
         if k is not None and not _topdown_covered(fine, coarse):
-            if fused:
-                raise NotImplementedError(f"fused=True: the top-down step from {tuple(coarse.shape)} {coarse.dtype} to {tuple(fine.shape)} "
-                                          f"{fine.dtype} is outside the kernels' coverage (a level exactly twice the next one, fp32 / bf16 maps)")
-            return None
+            return uncovered(self.fused, f"the top-down step from {tuple(coarse.shape)} {coarse.dtype} to {tuple(fine.shape)} {fine.dtype}",
+                             "a level exactly twice the next one, fp32 / bf16 maps")
         return k
 
     def _merge(self, fine, coarse):
@@ -142,7 +126,7 @@ class FPN(nn.Module):
         k = self._topdown_backend(fine, coarse)
         if k is None:
             return fine + F.interpolate(coarse, size=fine.shape[2:], mode="nearest")
-        return _TopDownFn.apply(fine, coarse, k)
+        return TopDownFn.apply(fine, coarse, k)
 
     def forward(self, inputs):
         assert len(inputs) == self.num_ins, f"FPN takes {self.num_ins} maps, got {len(inputs)}"

@@ -20,12 +20,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .conv import _rows_bf16
-from .det_backend import kernel_ops
-from .neck import EPI_BF16, EPI_F32, _version, _wgrad
+from .det_layer import BF16, EPI_BF16, EPI_RELU_BF16, F32, KernelLayer, bias_f32, epi_for, packed, pad_cols, rows2d, rows_bf16, wgrad
 
-BF16, F32 = torch.bfloat16, torch.float32
-EPI_RELU_BF16 = 9
 ACTS = {None: EPI_BF16, "relu": EPI_RELU_BF16}
 
 # Whether fused=None takes the kernels where the backend has them: set from profiles/fc_bench.md by the rule of FUSED_CONV_DEFAULT -- on only
@@ -65,7 +61,7 @@ def unpack_wgrad(dWp, spatial=None):
     return dWp.view(dWp.shape[0], P, C).permute(0, 2, 1).reshape(dWp.shape[0], C * P)
 
 
-class LinearAct(nn.Linear):
+class LinearAct(KernelLayer, nn.Linear):
     """nn.Linear(in_features, out_features) -- its parameters, names, initialisation and state dict -- followed by `act` (None or "relu"),
     whose forward and backward run on the HIP kernels when the tensors live on a backend with LINEAR_ACT, in_features % 64 == 0 and
     out_features % 8 == 0 (what cs_gemm_nt and cs_gemm_wgrad_tn take); F.linear (+ F.relu) otherwise.
@@ -74,6 +70,8 @@ class LinearAct(nn.Linear):
     fused:   True = the kernels or NotImplementedError, False = torch, None = FUSED_FC_DEFAULT where the kernels can run.
     splits:  K slices of the forward GEMM; None = chosen by the library, an integer forces it (the benchmark, the tests).
     forward(x): x [..., in_features] (or the map) fp32 / bf16 -> [..., out_features] of x's dtype; on the kernel route the values are bf16's."""
+    FLAG = "LINEAR_ACT"
+    COVERAGE = "in % 64 == 0, out % 8 == 0, fp32 parameters, fp32 / bf16 input"
 
     def __init__(self, in_features, out_features, bias=True, act=None, spatial=None, ops=None, fused=None, splits=None, **kw):
         super().__init__(in_features, out_features, bias=bias, **kw)
@@ -86,7 +84,6 @@ class LinearAct(nn.Linear):
         self.ops = ops
         self.fused = fused
         self.splits = splits
-        self._wcache = None
 
     def extra_repr(self):
         return super().extra_repr() + f", act={self.act}, spatial={self.spatial}"
@@ -101,21 +98,11 @@ class LinearAct(nn.Linear):
         return (self.in_features % 64 == 0 and self.out_features % 8 == 0 and self.weight.dtype == F32 and x.dtype in (F32, BF16)
                 and shape_ok and x.numel() > 0 and x.device == self.weight.device)
 
-    def kernel_backend(self, x):
-        """The backend whose LINEAR_ACT kernels serve forward(x), or None (-> torch); NotImplementedError where fused=True cannot be met."""
-        ops, fused = self.ops, self.fused
-        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "LINEAR_ACT", False) \
-                and ops.empty((1,), F32).device == x.device:
-            k = ops if fused or FUSED_FC_DEFAULT else None            # a host backend (the tests' reference ops) serves host tensors
-        else:
-            k = kernel_ops(x, "LINEAR_ACT", ops, fused, FUSED_FC_DEFAULT)
-        if k is not None and not self.covered(x):
-            if fused:
-                raise NotImplementedError(f"fused=True: LinearAct({self.in_features}, {self.out_features}, spatial={self.spatial}) on {x.dtype} "
-                                          f"{tuple(x.shape)} is outside the kernels' coverage (in % 64 == 0, out % 8 == 0, fp32 parameters, "
-                                          "fp32 / bf16 input)")
-            return None
-        return k
+    def describe(self):
+        return f"LinearAct({self.in_features}, {self.out_features}, spatial={self.spatial})"
+
+    def fused_default(self):
+        return FUSED_FC_DEFAULT
 
     def forward(self, x):
         k = self.kernel_backend(x)
@@ -128,14 +115,7 @@ class LinearAct(nn.Linear):
     def gemm_weights(self):
         """(Wp bf16 [out, in], WpT bf16 [in, out rounded up to 64], bias fp32 [out] | None), see pack_weights.  Rebuilt when the parameters'
         version counters (or their storage) change."""
-        w, b = self.weight, self.bias
-        key = (w.data_ptr(), _version(w), w.device, None if b is None else (b.data_ptr(), _version(b)))
-        if self._wcache is None or self._wcache[0] != key:
-            with torch.no_grad():
-                Wp, WpT = pack_weights(w, self.spatial)
-                bias = None if b is None else b.detach().to(F32).contiguous()
-            self._wcache = (key, Wp, WpT, bias)
-        return self._wcache[1:]
+        return packed(self, lambda: (*pack_weights(self.weight, self.spatial), bias_f32(self.bias)))
 
     def _splitk_ws(self, ops, M, N, K):
         """(splits argument, fp32 workspace | None) of the forward GEMM: the module's own grow-only buffer of splits * M * N floats."""
@@ -148,27 +128,15 @@ class LinearAct(nn.Linear):
         return (0 if self.splits is None else s), ws
 
 
-def _rows2d(ops, x, width):
-    """x [..., width] fp32 / bf16 -> bf16 rows [rows, width] with 16-byte aligned rows: a view where x allows it, one cast kernel for fp32."""
-    X = x.reshape(-1, width)
-    if X.dtype == BF16:
-        if X.stride(1) != 1 or X.stride(0) % 8 or X.data_ptr() % 16:
-            X = X.contiguous()
-        return X
-    out = ops.empty(tuple(X.shape), BF16)
-    ops.cast_f32_bf16(X.contiguous(), out)
-    return out
-
-
 class _LinearActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, mod, ops):
         inf, out = mod.in_features, mod.out_features
         Wp, _, b32 = mod.gemm_weights()
         if mod.spatial is not None:
-            X = _rows_bf16(ops, x).reshape(x.shape[0], inf)            # [K*P, C] seen as [K, P*C]: no data moves for a channel-last bf16 map
+            X = rows_bf16(ops, x).reshape(x.shape[0], inf)             # [K*P, C] seen as [K, P*C]: no data moves for a channel-last bf16 map
         else:
-            X = _rows2d(ops, x, inf)
+            X = rows2d(ops, x, inf)
         rows = X.shape[0]
         Y = ops.empty((rows, out), BF16)
         splits, ws = mod._splitk_ws(ops, rows, out, inf)
@@ -187,18 +155,16 @@ class _LinearActFn(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
         dY = d_out.reshape(rows, out)
         dZ = relu_gate(Y, dY) if mod.act == "relu" else dY.to(BF16)
-        outp = (out + 63) // 64 * 64
-        if outp != out:                                                # zero columns pad the dgrad's contraction to the K tile
-            dZp = ops.zeros((rows, outp), BF16)
-            dZp[:, :out] = dZ
-            dZ = dZp[:, :out]
-        else:
+        dZp = pad_cols(ops, dZ)                                        # zero columns pad the dgrad's contraction to the K tile
+        if dZp is dZ:
             dZp = dZ = dZ.contiguous()
+        else:
+            dZ = dZp[:, :out]
         dx = dw = db = None
         if need_x:
             _, WpT, _ = mod.gemm_weights()
             dX = ops.empty((rows, inf), ctx.x_dtype)
-            ops.gemm_nt(dZp, WpT, dX, None, epi=EPI_F32 if ctx.x_dtype == F32 else EPI_BF16)
+            ops.gemm_nt(dZp, WpT, dX, None, epi=epi_for(ctx.x_dtype))
             if mod.spatial is not None:
                 K, C, h, w = ctx.x_shape
                 dx = dX.view(K, h, w, C).permute(0, 3, 1, 2)             # the channel-last map: the batch norm in front takes it in place
@@ -206,7 +172,7 @@ class _LinearActFn(torch.autograd.Function):
                 dx = dX.view(ctx.x_shape)
         if need_w:
             dWp = ops.zeros((out, inf), F32)
-            _wgrad(ops, mod, dZ, X, dWp)
+            wgrad(ops, mod, dZ, X, dWp)
             dw = unpack_wgrad(dWp, mod.spatial)
         if need_b:
             db = ops.zeros((out,), F32)

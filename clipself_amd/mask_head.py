@@ -11,7 +11,7 @@ laying the [K, C, 28, 28] map out:
     2. that buffer as rows [4*K*196, C] through HipOps.thin_fwd (rows form, N = 1 | num_classes <= 16): the logits, 4 bytes per pixel;
     3. a torch permutation of the [K, 14, 14, 2, 2, N] logits to [K, N, 28, 28].
 The backward is the inverse permutation, HipOps.thin_dgrad with the saved activation as the ReLU's gate, the deconvolution's own
-pieces (neck._wgrad, colsum_bf16, gemm_nt with Wg^T) on those rows, and conv_logits' gradients as in conv.Conv1x1Thin.
+pieces (det_layer.wgrad, colsum_bf16, gemm_nt with Wg^T) on those rows, and conv_logits' gradients as in conv.Conv1x1Thin.
 
 The initialisation follows mmdet's FCNMaskHead.init_weights (Kaiming normal, mode='fan_out', nonlinearity='relu', zero biases for
 `upsample` and `conv_logits`).  mmdet is not installed beside this project, so that part is cited, not run: parity-unpinned.
@@ -22,19 +22,17 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .conv import THIN_MAX_N, Conv1x1, Conv1x1Thin, _rows_bf16, _row_chunks, thin_param_grads
-from .fpn import NORMS
-from .neck import BF16, EPI_BF16, EPI_F32, F32, Deconv2x2, _wgrad
-from .norm_act import ConvModule
-
-EPI_RELU_BF16 = 9                             # cs_gemm_nt: C = bf16(relu(acc + bias))
+from .conv import THIN_MAX_N, Conv1x1, Conv1x1Thin, thin_param_grads
+from .det_layer import BF16, EPI_RELU_BF16, F32, epi_for, row_chunks, rows_bf16, rows_to_map, uncovered, wgrad
+from .neck import Deconv2x2
+from .norm_act import ConvModule, apply_norm_cfg
 
 
 class FCNMaskHead(nn.Module):
     """FCNMaskHead(**the config's mask_head dict).  forward(x [K, in_channels, s, s]) -> mask logits [K, 1 | num_classes, 2s, 2s]; fp32
     on the kernel route.
 
-    ops / fused are handed to every kernel-backed submodule (see conv.Conv3x3.fused); the fused tail additionally needs
+    ops / fused are handed to every kernel-backed submodule (see det_layer.KernelLayer); the fused tail additionally needs
     conv_out_channels % 64 == 0 and a logits width <= 16."""
 
     def __init__(self, num_convs=4, in_channels=256, conv_out_channels=256, num_classes=80, class_agnostic=False, norm_cfg=None,
@@ -49,8 +47,6 @@ class FCNMaskHead(nn.Module):
             raise NotImplementedError(f"FCNMaskHead: upsample_cfg={upsample_cfg!r} is not built here (dict(type='deconv', scale_factor=2) only)")
         if other_modules.get("conv_kernel_size", 3) != 3:
             raise NotImplementedError(f"FCNMaskHead: conv_kernel_size={other_modules['conv_kernel_size']!r} is not built here (3 only)")
-        if norm_cfg is not None and norm_cfg.get("type") not in NORMS:
-            raise NotImplementedError(f"FCNMaskHead: norm_cfg={norm_cfg!r} is not built here (type one of {NORMS}, or norm_cfg=None)")
         self.num_convs, self.in_channels, self.conv_out_channels = num_convs, in_channels, conv_out_channels
         self.num_classes, self.class_agnostic = num_classes, class_agnostic
         self.ops, self.fused = ops, fused
@@ -63,10 +59,7 @@ class FCNMaskHead(nn.Module):
             self.conv_logits = Conv1x1Thin(conv_out_channels, width, ops=ops, fused=fused)
         else:
             self.conv_logits = Conv1x1(conv_out_channels, width, ops=ops, fused=fused)
-        if norm_cfg is not None and not norm_cfg.get("requires_grad", True):      # build_norm_layer: param.requires_grad = requires_grad
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.requires_grad_(False)
+        apply_norm_cfg(self, norm_cfg)
         self.init_weights()
 
     def init_weights(self):
@@ -86,10 +79,8 @@ class FCNMaskHead(nn.Module):
         ok = (getattr(k, "LINEAR_ACT", False) and up.in_channels % 64 == 0 and up.out_channels % 64 == 0 and up.weight.dtype == F32
               and up.weight.device == x.device and up.bias is not None)
         if not ok:
-            if self.fused:
-                raise NotImplementedError(f"fused=True: FCNMaskHead's tail ({up.in_channels} -> {up.out_channels} -> {lg.out_channels}) is "
-                                          "outside the kernels' coverage (channels % 64 == 0, fp32 parameters, a backend with LINEAR_ACT)")
-            return None
+            return uncovered(self.fused, f"FCNMaskHead's tail ({up.in_channels} -> {up.out_channels} -> {lg.out_channels})",
+                             "channels % 64 == 0, fp32 parameters, a backend with LINEAR_ACT")
         return k
 
     def forward(self, x):
@@ -110,12 +101,12 @@ class _MaskTailFn(torch.autograd.Function):
         Cout, Nl, M = up.out_channels, lg.out_channels, K * h * w
         Wg, _, bias4 = up.gemm_weights()
         Wl, bl = lg.gemm_weights()
-        X = _rows_bf16(ops, x)
+        X = rows_bf16(ops, x)
         keep = any(ctx.needs_input_grad[:5])
         act = ops.empty((M, 4 * Cout), BF16) if keep else None              # relu(deconv) on the rows: the gate and conv_logits' operand
         L = ops.empty((4 * M, Nl), F32)
         buf = None
-        for r0, n in _row_chunks(M, 4 * Cout * 2):
+        for r0, n in row_chunks(M, 4 * Cout * 2):
             if keep:
                 Y = act[r0:r0 + n]
             else:
@@ -152,7 +143,7 @@ class _MaskTailFn(torch.autograd.Function):
             dY = dA.view(M, 4 * Cout)
             if need_uw:
                 dWg = ops.zeros((4 * Cout, Cin), F32)
-                _wgrad(ops, up, dY, X, dWg)
+                wgrad(ops, up, dY, X, dWg)
                 duw = dWg.view(2, 2, Cout, Cin).permute(3, 2, 0, 1).contiguous()
             if need_ub:
                 col = ops.zeros((4 * Cout,), F32)
@@ -160,6 +151,6 @@ class _MaskTailFn(torch.autograd.Function):
                 dub = col.view(4, Cout).sum(0)
             if need_x:
                 dXr = ops.empty((M, Cin), ctx.x_dtype)
-                ops.gemm_nt(dY, WgT, dXr, None, epi=EPI_F32 if ctx.x_dtype == F32 else EPI_BF16)
-                dx = dXr.view(K, h, w, Cin).permute(0, 3, 1, 2)
+                ops.gemm_nt(dY, WgT, dXr, None, epi=epi_for(ctx.x_dtype))
+                dx = rows_to_map(dXr, K, h, w)
         return dx, duw, dub, dlw, dlb, None, None

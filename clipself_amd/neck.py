@@ -16,9 +16,8 @@ from typing import NamedTuple
 import torch
 from torch import nn
 
-BF16, F32 = torch.bfloat16, torch.float32
-EPI_BF16, EPI_F32 = 0, 1                      # cs_gemm_nt epilogues: C = bf16(acc + bias) / C = acc + bias in fp32
-CHUNK_BYTES = 512 << 20                       # upper bound of an intermediate rows buffer (Y, dY); images are processed in chunks under it
+from .det_layer import CHUNK_BYTES  # noqa: F401  (the bound of a rows buffer keeps its public name here)
+from .det_layer import BF16, F32, backend_device, epi_for, kernel_grad, packed, row_chunks, wgrad
 
 
 class TokenRows(NamedTuple):
@@ -36,13 +35,6 @@ class TokenRows(NamedTuple):
         return self.rows.view(self.B, self.h * self.w + self.off, C)[:, self.off:].permute(0, 2, 1).reshape(self.B, C, self.h, self.w).to(dtype)
 
 
-def _version(t):
-    try:
-        return t._version
-    except RuntimeError:                       # inference tensors carry no version counter
-        return -1
-
-
 class Deconv2x2(nn.ConvTranspose2d):
     """nn.ConvTranspose2d(Cin, Cout, kernel_size=2, stride=2) -- its parameters, names, initialisation and state dict -- whose forward and
     backward run as GEMMs on token rows when `ops` (a kernel backend with DECONV_ROWS) is set, the tensors live on that backend's device,
@@ -55,23 +47,15 @@ class Deconv2x2(nn.ConvTranspose2d):
             and self.dilation == (1, 1) and self.groups == 1 and self.padding_mode == "zeros", "Deconv2x2 is ConvTranspose2d(k=2, s=2) and nothing else"
         self.ops = ops
         self.out_dtype = out_dtype
-        self._wcache = None
 
     # ------------------------------------------------------------------------------------------ dispatch
-    def _ops_device(self):
-        ops = self.ops
-        dev = getattr(ops, "_deconv_device", None)
-        if dev is None:
-            dev = ops._deconv_device = ops.empty((1,), F32).device
-        return dev
-
     def fused_rows(self) -> bool:
         """True when a TokenRows on the backend's device would take the GEMM path: what the owner asks before it orders rows from the tower."""
         if self.ops is None or not getattr(self.ops, "DECONV_ROWS", False):
             return False
         if self.in_channels % 64 or self.out_channels % 16 or self.weight.dtype != F32:
             return False
-        return self.weight.device == self._ops_device()
+        return self.weight.device == backend_device(self.ops)
 
     def fused(self, x) -> bool:
         """True when forward(x) takes the GEMM path."""
@@ -80,7 +64,7 @@ class Deconv2x2(nn.ConvTranspose2d):
         t = x.rows if isinstance(x, TokenRows) else x
         if not isinstance(x, TokenRows) and (t.dim() != 4 or t.dtype not in (F32, BF16)):
             return False
-        return t.device == self._ops_device()
+        return t.device == backend_device(self.ops)
 
     def forward(self, x, output_size=None):
         if output_size is None and self.fused(x):
@@ -98,22 +82,14 @@ class Deconv2x2(nn.ConvTranspose2d):
     def gemm_weights(self):
         """(Wg bf16 [4*Cout, Cin], Wg^T bf16 [Cin, 4*Cout], bias4 fp32 [4*Cout] | None): Wg[(2*di + dj)*Cout + co, ci] = weight[ci, co, di, dj].
         Rebuilt when the parameters' version counters (or their storage) change."""
-        w, b = self.weight, self.bias
-        key = (w.data_ptr(), _version(w), w.device, None if b is None else (b.data_ptr(), _version(b)))
-        if self._wcache is None or self._wcache[0] != key:
-            with torch.no_grad():
-                Cin, Cout = self.in_channels, self.out_channels
-                wb = w.detach().to(BF16)
-                Wg = wb.permute(2, 3, 1, 0).reshape(4 * Cout, Cin).contiguous()
-                WgT = wb.permute(0, 2, 3, 1).reshape(Cin, 4 * Cout).contiguous()
-                bias4 = None if b is None else b.detach().to(F32).repeat(4).contiguous()
-            self._wcache = (key, Wg, WgT, bias4)
-        return self._wcache[1:]
+        return packed(self, self._pack)
 
-
-def _chunks(B, rows_per_image, row_bytes):
-    nb = max(1, min(B, CHUNK_BYTES // max(1, rows_per_image * row_bytes)))
-    return [(b0, min(nb, B - b0)) for b0 in range(0, B, nb)]
+    def _pack(self):
+        Cin, Cout, b = self.in_channels, self.out_channels, self.bias
+        wb = self.weight.detach().to(BF16)
+        Wg = wb.permute(2, 3, 1, 0).reshape(4 * Cout, Cin).contiguous()
+        WgT = wb.permute(0, 2, 3, 1).reshape(Cin, 4 * Cout).contiguous()
+        return Wg, WgT, None if b is None else b.detach().to(F32).repeat(4).contiguous()
 
 
 class _DeconvFn(torch.autograd.Function):
@@ -131,9 +107,9 @@ class _DeconvFn(torch.autograd.Function):
         R = h * w + off
         out = ops.empty((B, Cout, 2 * h, 2 * w), out_dtype)
         esize = 4 if out_dtype == F32 else 2
-        epi = EPI_F32 if out_dtype == F32 else EPI_BF16
+        epi = epi_for(out_dtype)
         Y = None
-        for b0, nb in _chunks(B, R, 4 * Cout * esize):
+        for b0, nb in row_chunks(B, R * 4 * Cout * esize):                   # whole images per chunk
             if Y is None or Y.shape[0] != nb * R:
                 Y = ops.empty((nb * R, 4 * Cout), out_dtype)
             ops.gemm_nt(X[b0 * R:(b0 + nb) * R], Wg, Y, bias4, epi=epi)
@@ -152,50 +128,27 @@ class _DeconvFn(torch.autograd.Function):
         (X,) = ctx.saved_tensors
         R = h * w + off
         need_x, need_w, need_b = ctx.needs_input_grad[0] and ctx.x_nchw, ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
-        if d_out.dtype not in (F32, BF16):
-            d_out = d_out.to(F32)
-        d_out = d_out.contiguous()
+        d_out = kernel_grad(d_out).contiguous()
         _, WgT, _ = mod.gemm_weights()
         dWg = ops.zeros((4 * Cout, Cin), F32) if need_w else None
         col = ops.zeros((4 * Cout,), F32) if need_b else None
         dx = ops.empty((B, Cin, h, w), ctx.x_dtype) if need_x else None
         dY = dXr = None
-        for b0, nb in _chunks(B, R, 4 * Cout * 2):
+        for b0, nb in row_chunks(B, R * 4 * Cout * 2):
             M = nb * R
             if dY is None or dY.shape[0] != M:
                 dY = ops.empty((M, 4 * Cout), BF16)
             ops.nchw_to_rows(d_out[b0:b0 + nb], nb, h, w, Cout, 2, off, dY)
             if need_w:
-                _wgrad(ops, mod, dY, X[b0 * R:(b0 + nb) * R], dWg)
+                wgrad(ops, mod, dY, X[b0 * R:(b0 + nb) * R], dWg)
             if need_b:
                 ops.colsum_bf16(dY, col)
             if need_x:
                 if dXr is None or dXr.shape[0] != M:
                     dXr = ops.empty((M, Cin), ctx.x_dtype)
-                ops.gemm_nt(dY, WgT, dXr, None, epi=EPI_F32 if ctx.x_dtype == F32 else EPI_BF16)
+                ops.gemm_nt(dY, WgT, dXr, None, epi=epi_for(ctx.x_dtype))
                 ops.rows_to_nchw(dXr, nb, h, w, Cin, 1, 0, dx[b0:b0 + nb])
         dw = dWg.view(2, 2, Cout, Cin).permute(3, 2, 0, 1).contiguous() if need_w else None
         db = col.view(4, Cout).sum(0) if need_b else None
         return dx, dw, db, None, None, None
 
-
-def _wgrad(ops, mod, dY, X, dW):
-    """dW[N, K] += dY^T . X from the token-major operands; shapes cs_gemm_wgrad_tn does not cover go through explicit transposes and the NT
-    split-K kernel (as TowerEngine._wgrad)."""
-    M, N = dY.shape
-    K = X.shape[1]
-    ws = mod.__dict__.get("_wgrad_ws")
-    need = ops.gemm_wgrad_tn_workspace(N, K, M)
-    tn = need > 0
-    if not tn:
-        Mp = (M + 63) // 64 * 64
-        need = ops.gemm_wgrad_workspace(N, K, Mp)
-    if ws is None or ws.numel() < need or ws.device != dY.device:
-        ws = mod.__dict__["_wgrad_ws"] = ops.empty((need,), torch.uint8)
-    if tn:
-        ops.gemm_wgrad_tn(dY, X, dW, ws)
-        return
-    Xt, dYt = ops.empty((K, Mp), BF16), ops.empty((N, Mp), BF16)
-    ops.transpose_bf16(X, Xt)
-    ops.transpose_bf16(dY, dYt)
-    ops.gemm_wgrad(dYt, Xt, dW, ws)

@@ -20,10 +20,10 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
-from .conv import Conv1x1, Conv3x3, _is_channel_last
-from .det_backend import kernel_ops
+from .conv import Conv1x1, Conv3x3
+from .det_layer import BF16, F32, KernelLayer, channel_last_rows, kernel_grad, rows_to_map
 
-BF16, F32 = torch.bfloat16, torch.float32
+NORMS = ("BN", "SyncBN", "MMSyncBN")          # what build_norm_layer abbreviates to `bn`: all of them are BatchNormAct2d here
 REC_EXTRA, ST_EXTRA = 4, 4          # include/clipself_bn.h: a record is 2*C + 4 floats, a state 4*C + 4
 ACTS = {None: 0, "relu": 1}
 
@@ -36,7 +36,7 @@ ACTS = {None: 0, "relu": 1}
 FUSED_BN_DEFAULT = True
 
 
-class BatchNormAct2d(nn.BatchNorm2d):
+class BatchNormAct2d(KernelLayer, nn.BatchNorm2d):
     """nn.BatchNorm2d (training semantics of nn.SyncBatchNorm when torch.distributed runs with more than one rank) followed by `act`
     (None or "relu"), on the HIP kernels when the tensors live on a backend with BATCHNORM and the case is covered: C % 8 == 0, a momentum
     that is a number, an fp32 / bf16 input, fp32 parameters and buffers.  F.batch_norm (+ F.relu) otherwise.
@@ -44,6 +44,8 @@ class BatchNormAct2d(nn.BatchNorm2d):
     fused: True = the kernels or NotImplementedError, False = torch, None = FUSED_BN_DEFAULT where the kernels can run.
     forward(x): x [N, C, H, W] -> [N, C, H, W] of x's dtype with channel-last strides (kernel route).  A channel-last x is used in place,
     anything else is made channel-last once by torch."""
+    FLAG = "BATCHNORM"
+    COVERAGE = "C % 8 == 0, a numeric momentum, fp32 / bf16 input, fp32 parameters and buffers"
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, act=None, process_group=None, ops=None,
                  fused=None, **kw):
@@ -63,21 +65,11 @@ class BatchNormAct2d(nn.BatchNorm2d):
         return (self.num_features % 8 == 0 and self.momentum is not None and x.dim() == 4 and x.dtype in (F32, BF16)
                 and x.shape[1] == self.num_features and x.numel() > 0 and all(t.dtype == F32 and t.device == x.device for t in tensors))
 
-    def kernel_backend(self, x):
-        """The backend whose BATCHNORM kernels serve forward(x), or None (-> torch); NotImplementedError where fused=True cannot be met."""
-        ops, fused = self.ops, self.fused
-        if fused is not False and ops is not None and not x.is_cuda and getattr(ops, "BATCHNORM", False) \
-                and ops.empty((1,), F32).device == x.device:
-            k = ops if fused or FUSED_BN_DEFAULT else None            # a host backend (the tests' reference ops) serves host tensors
-        else:
-            k = kernel_ops(x, "BATCHNORM", ops, fused, FUSED_BN_DEFAULT)
-        if k is not None and not self.covered(x):
-            if fused:
-                raise NotImplementedError(f"fused=True: BatchNormAct2d({self.num_features}, momentum={self.momentum}) on {x.dtype} "
-                                          f"{tuple(x.shape)} is outside the kernels' coverage (C % 8 == 0, a numeric momentum, fp32 / bf16 "
-                                          "input, fp32 parameters and buffers)")
-            return None
-        return k
+    def describe(self):
+        return f"BatchNormAct2d({self.num_features}, momentum={self.momentum})"
+
+    def fused_default(self):
+        return FUSED_BN_DEFAULT
 
     def forward(self, x):
         k = self.kernel_backend(x)
@@ -119,14 +111,7 @@ class BatchNormAct2d(nn.BatchNorm2d):
         return sums
 
 
-def _rows(t):
-    """t [N, C, H, W] -> (its rows [N*H*W, C] as a view of a channel-last tensor, made channel-last by torch where it is not)."""
-    if not _is_channel_last(t):
-        t = t.contiguous(memory_format=torch.channels_last)
-        if not _is_channel_last(t):                                   # torch keeps ambiguous strides (C == 1 or H == W == 1) as they are
-            t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    N, C, H, W = t.shape
-    return t.permute(0, 2, 3, 1).reshape(N * H * W, C)
+_rows = channel_last_rows                      # the name it had here, for callers written before it moved to det_layer
 
 
 class _BatchNormActFn(torch.autograd.Function):
@@ -135,7 +120,7 @@ class _BatchNormActFn(torch.autograd.Function):
         N, C, H, W = x.shape
         M = N * H * W
         act = ACTS[mod.act]
-        X = _rows(x)
+        X = channel_last_rows(x)
         gamma = None if weight is None else weight.detach()
         beta = None if bias is None else bias.detach()
         block = ops.empty((6 * C + ST_EXTRA + REC_EXTRA,), F32)          # the state and this rank's record: one allocation
@@ -154,16 +139,14 @@ class _BatchNormActFn(torch.autograd.Function):
         ctx.mod, ctx.ops, ctx.act, ctx.geom, ctx.batch_stats = mod, ops, act, (N, H, W, C), batch_stats
         ctx.affine = (weight is not None, bias is not None)
         ctx.save_for_backward(X, st, gamma)
-        return Y.view(N, H, W, C).permute(0, 3, 1, 2)
+        return rows_to_map(Y, N, H, W)
 
     @staticmethod
     def backward(ctx, d_out):
         mod, ops, act = ctx.mod, ctx.ops, ctx.act
         N, H, W, C = ctx.geom
         X, st, gamma = ctx.saved_tensors
-        if d_out.dtype not in (F32, BF16):
-            d_out = d_out.to(F32)
-        dY = _rows(d_out)
+        dY = channel_last_rows(kernel_grad(d_out))
         sums = ops.empty((2 * C,), F32)
         ops.bn_bwd_reduce(dY, X, st, act, sums)
         reduce = ctx.needs_input_grad[0] and ctx.batch_stats and mod._syncs()
@@ -176,8 +159,21 @@ class _BatchNormActFn(torch.autograd.Function):
                 sums = mod._reduce_sums(sums)
             dX = ops.empty((N * H * W, C), X.dtype)
             ops.bn_bwd_apply(dY, X, st, act, sums, gamma, dX)
-            dx = dX.view(N, H, W, C).permute(0, 3, 1, 2)
+            dx = rows_to_map(dX, N, H, W)
         return dx, dgamma, dbeta, None, None, None
+
+
+def apply_norm_cfg(owner, norm_cfg):
+    """What a head does with its config's norm_cfg once its layers stand: a type outside NORMS is refused in the owner's name, and
+    requires_grad=False freezes every batch norm's parameters (build_norm_layer: param.requires_grad = requires_grad)."""
+    if norm_cfg is None:
+        return
+    if norm_cfg.get("type") not in NORMS:
+        raise NotImplementedError(f"{type(owner).__name__}: norm_cfg={norm_cfg!r} is not built here (type one of {NORMS}, or norm_cfg=None)")
+    if not norm_cfg.get("requires_grad", True):
+        for m in owner.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.requires_grad_(False)
 
 
 class ConvModule(nn.Module):

@@ -23,8 +23,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .conv import Conv1x1Thin, Conv3x3, thin_heads
-from .fpn import NORMS
-from .norm_act import ConvModule
+from .norm_act import ConvModule, apply_norm_cfg
 
 
 class RPNHead(nn.Module):
@@ -32,7 +31,7 @@ class RPNHead(nn.Module):
     [B, 4 A, h, w]; contiguous NCHW fp32 on the kernel route.  mmdet's forward_single applies F.relu after rpn_conv; behind a ConvModule
     that ends in ReLU it is the identity and is skipped.
 
-    ops / fused are handed to every kernel-backed submodule (see conv.Conv3x3.fused)."""
+    ops / fused are handed to every kernel-backed submodule (see det_layer.KernelLayer)."""
 
     def __init__(self, in_channels, feat_channels=256, anchor_generator=None, num_convs=1, norm_cfg=None, ops=None, fused=None,
                  # What belongs to other modules here and is accepted so that a config dict can be passed whole:
@@ -44,8 +43,6 @@ class RPNHead(nn.Module):
         super().__init__()
         if anchor_generator is None:
             anchor_generator = dict(scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64])     # mmdet's AnchorHead default
-        if norm_cfg is not None and norm_cfg.get("type") not in NORMS:
-            raise NotImplementedError(f"RPNHead: norm_cfg={norm_cfg!r} is not built here (type one of {NORMS}, or norm_cfg=None)")
         scales = anchor_generator.get("scales")
         if scales is None:                                                # AnchorGenerator: octave_base_scale * 2^(i / scales_per_octave)
             scales = range(anchor_generator["scales_per_octave"])
@@ -60,10 +57,7 @@ class RPNHead(nn.Module):
             self.rpn_conv = Conv3x3(in_channels, feat_channels, ops=ops, fused=fused)
         self.rpn_cls = Conv1x1Thin(feat_channels, self.num_base_priors * self.cls_out_channels, ops=ops, fused=fused)
         self.rpn_reg = Conv1x1Thin(feat_channels, self.num_base_priors * 4, ops=ops, fused=fused)
-        if norm_cfg is not None and not norm_cfg.get("requires_grad", True):      # build_norm_layer: param.requires_grad = requires_grad
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.requires_grad_(False)
+        apply_norm_cfg(self, norm_cfg)
         self.init_weights()
 
     def init_weights(self):

@@ -12,7 +12,7 @@ from torch import nn
 from _bn_ref import (BF, EPS, EXACT_IDS, EXACT_PARTS, EXACT_SHAPES, F32, MOMENTUM, SHAPE_IDS, SHAPES, RefOpsBN, all_bits, case, check_exact,
                      check_ops, flawed, make_parts_bn, offset_operands, random_operands, reference, run_exact, run_ops)
 from _neck_ref import check_bound
-from clipself_amd import norm_act
+from clipself_amd import det_layer, norm_act
 from clipself_amd.norm_act import BatchNormAct2d, ConvModule
 
 UNBALANCED = (1, 37, 90)                    # three parts of 128 rows
@@ -148,7 +148,7 @@ def test_checks_reject_parameter_gradients_taken_after_the_cross_part_sum(monkey
             mod, ops, act = ctx.mod, ctx.ops, ctx.act
             N, H, W, C = ctx.geom
             X, st, gamma = ctx.saved_tensors
-            dY = norm_act._rows(d_out)
+            dY = det_layer.channel_last_rows(d_out)
             sums = ops.empty((2 * C,), F32)
             ops.bn_bwd_reduce(dY, X, st, act, sums)
             sums = mod._reduce_sums(sums)

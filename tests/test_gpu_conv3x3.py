@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 from _conv_ref import (BF, F32, ROUTES, SHAPE_IDS, SHAPES, bounds, case, check_bound, index_im2col, layer, map_of, rne_bf16,  # noqa: E402
                        rows_of, run_layer, same_bits)
 from _extents import run_case  # noqa: E402
-from clipself_amd.conv import _pad_k, pack_weights  # noqa: E402
+from clipself_amd.conv import pack_weights  # noqa: E402
+from clipself_amd.det_layer import pad_cols  # noqa: E402
 
 EPI = {BF: 0, F32: 1}
 
@@ -46,7 +47,7 @@ def _conv_rows(hip, route, X, Wm, bias, N, H, W, dtype):
     if route == "implicit":
         hip.conv3x3(X, Wm, out, bias, N, H, W)
         return out
-    Wp = _pad_k(Wm)
+    Wp = pad_cols(hip, Wm)
     cols = torch.zeros(M, Wp.shape[1], dtype=BF, device="cuda")
     cols[:, :9 * Ci] = float("nan")
     hip.im2col3x3(X, cols[:, :9 * Ci], N, H, W)

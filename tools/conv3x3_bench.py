@@ -141,10 +141,10 @@ def main(argv=None):
         print(f"| {k} | {med:.0f} ({min(v):.0f} .. {max(v):.0f}) | {tf:.0f} | {100 * tf * 1e12 / PEAK_BF16:.1f} % |" if gemm else
               f"| {k} | {med:.0f} ({min(v):.0f} .. {max(v):.0f}) | {M * K * 2 / med / 1e6:.2f} TB/s written | |")
     # the launches of one backward on the implicit route at the box head's shape (fp32 upstream gradient, fp32 dx), each timed alone
-    from clipself_amd.conv import _row_chunks
+    from clipself_amd.det_layer import row_chunks
     dY32 = torch.randn(M, C, generator=g).cuda()
     dY, dX, dWg, db = torch.empty(M, C, dtype=BF16, device="cuda"), torch.empty(M, C, device="cuda"), torch.zeros(C, K, device="cuda"), torch.zeros(C, device="cuda")
-    chunks = _row_chunks(M, K * 2)
+    chunks = row_chunks(M, K * 2)
     ws = torch.empty(max(ops.gemm_wgrad_tn_workspace(C, K, n) for _, n in chunks), dtype=torch.uint8, device="cuda")
 
     def im2col_chunks():

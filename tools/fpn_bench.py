@@ -95,8 +95,8 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--windows", type=int, default=9)
     args = ap.parse_args(argv)
-    from clipself_amd.conv import _rows_bf16
-    from clipself_amd.fpn import FPN, _TopDownFn
+    from clipself_amd.det_layer import rows_bf16
+    from clipself_amd.fpn import FPN, TopDownFn
     from clipself_amd.hip import HipOps
     ops = HipOps()
     print(f"windows of {args.iters} calls, {args.windows} windows, variants alternated; {ops.num_cus} compute units; B = {B}, "
@@ -165,7 +165,7 @@ def main(argv=None):
                 verdict_lat[name] = part_med[title]["all kernels"] < best
 
         # ---- the conversion in front of the laterals
-        conv = measure({"nchw_to_rows": lambda: [_rows_bf16(ops, x.detach()) for x in xs]}, args.iters, args.windows)["nchw_to_rows"]
+        conv = measure({"nchw_to_rows": lambda: [rows_bf16(ops, x.detach()) for x in xs]}, args.iters, args.windows)["nchw_to_rows"]
         lat = part_med["laterals (1x1 + norm)"]["all kernels"]
         print(f"\nNCHW fp32 -> bf16 rows of the four inputs (HipOps.nchw_to_rows): {fmt(conv)} µs = "
               f"{100 * statistics.median(conv) / lat:.1f} % of the kernel laterals' forward + backward ({lat:.0f} µs)")
@@ -186,7 +186,7 @@ def main(argv=None):
                     "form 7 (accumulate in place)": (lambda: ops.upsample2x_add(coarse, work, B, hs, hs, COUT, True), nb_c + 2 * nb_f),
                     "form 8 (overwrite)": (lambda: ops.pool2x(fine, pooled, B, hs, hs, COUT, False), nb_c + nb_f),
                     "torch fine + interpolate, forward": (lambda: fm.detach() + F.interpolate(cm.detach(), scale_factor=2, mode="nearest"), None),
-                    "kernels forward + backward (copy, form 7, form 8)": (step(lambda lv: [_TopDownFn.apply(lv[0], lv[1], ops)], [fm, cm], []),
+                    "kernels forward + backward (copy, form 7, form 8)": (step(lambda lv: [TopDownFn.apply(lv[0], lv[1], ops)], [fm, cm], []),
                                                                           2 * nb_f + nb_c + 2 * nb_f + nb_f + nb_c),
                     "torch forward + backward": (step(lambda lv: [lv[0] + F.interpolate(lv[1], scale_factor=2, mode="nearest")], [fm, cm], []), None),
                 }
