@@ -4,8 +4,10 @@ F-ViT/models/fvit_head.py:14 derives FViTBBoxHead from mmdet.models.roi_heads.Co
 module's lists: `shared_convs` (ConvModules), `x.flatten(1)`, `shared_fcs`, then the class branch (`cls_convs`, `cls_fcs`) and the box
 branch (`reg_convs`, `reg_fcs`, `fc_reg`), every FC followed by ReLU.  Here the ConvModules are norm_act.ConvModule (conv.Conv3x3 +
 norm_act.BatchNormAct2d), the FCs are linear.LinearAct(act="relu") -- the first shared FC with `spatial`, so the flatten moves no data --
-and `fc_reg` (512 -> 4, 16 MFLOP, outside the kernels' coverage) stays nn.Linear.  The submodules carry mmdet's names, so a reference
-checkpoint's box-head keys load with strict=True.
+and `fc_reg` (512 -> 4, 16 MFLOP) is linear.LinearThin where its width is <= 16 and its input a multiple of 64 (class-agnostic
+regression, every F-ViT config), nn.Linear otherwise.  `fc_reg` has a switch of its own, `fused_reg` (None = conv.FUSED_THIN_DEFAULT,
+which is off: F.linear); the head's `fused` is not handed to it.  The submodules carry mmdet's names, so a reference checkpoint's
+box-head keys load with strict=True.
 
 Two lines compose the training branch with ov_head.OpenVocabBoxScores:
 
@@ -20,7 +22,7 @@ from __future__ import annotations
 
 from torch import nn
 
-from .linear import LinearAct
+from .linear import THIN_MAX_N, LinearAct, LinearThin
 from .norm_act import ConvModule
 
 
@@ -28,11 +30,12 @@ class ConvFCBBoxHead(nn.Module):
     """ConvFCBBoxHead(**the config's bbox_head dict).  forward(x [K, in_channels, s, s]) -> (x_cls [K, fc_out_channels], bbox_pred [K, 4 |
     4 * num_classes]): fvit_head.py:72-107 up to the class branch's output, which goes to OpenVocabBoxScores.class_logits unchanged.
 
-    ops / fused are handed to every kernel-backed submodule (see det_layer.KernelLayer)."""
+    ops / fused are handed to every kernel-backed submodule (see det_layer.KernelLayer) but fc_reg, which takes ops / fused_reg; on its
+    kernel route bbox_pred is fp32 whatever the input's dtype."""
 
     def __init__(self, in_channels=256, fc_out_channels=1024, roi_feat_size=7, num_shared_convs=0, num_shared_fcs=0, num_cls_convs=0,
                  num_cls_fcs=0, num_reg_convs=0, num_reg_fcs=0, conv_out_channels=256, num_classes=80, reg_class_agnostic=False,
-                 norm_cfg=None, ops=None, fused=None,
+                 norm_cfg=None, ops=None, fused=None, fused_reg=None,
                  # What belongs to other modules here and is accepted so that a config dict can be passed whole:
                  #   bbox_coder                        -> det_post.delta2bbox / det_targets.bbox_targets
                  #   loss_cls, loss_bbox               -> det_losses.BBoxHeadLoss
@@ -52,7 +55,7 @@ class ConvFCBBoxHead(nn.Module):
         self.num_cls_convs, self.num_cls_fcs, self.num_reg_convs, self.num_reg_fcs = num_cls_convs, num_cls_fcs, num_reg_convs, num_reg_fcs
         self.num_classes, self.reg_class_agnostic = num_classes, reg_class_agnostic
         self.norm = norm_cfg is not None
-        self.ops, self.fused = ops, fused
+        self.ops, self.fused, self.fused_reg = ops, fused, fused_reg
 
         self.shared_convs, self.shared_fcs, last, spatial = self._branch(num_shared_convs, num_shared_fcs, in_channels, True)
         self.shared_out_channels = last
@@ -65,7 +68,11 @@ class ConvFCBBoxHead(nn.Module):
                 self.reg_last_dim *= self.roi_feat_area
         # fc_cls is part of the state dict and unused by the forward, as in FViTBBoxHead (the class scores come from the embeddings)
         self.fc_cls = nn.Linear(self.cls_last_dim, num_classes + 1)
-        self.fc_reg = nn.Linear(self.reg_last_dim, 4 if reg_class_agnostic else 4 * num_classes)
+        reg_width = 4 if reg_class_agnostic else 4 * num_classes
+        if reg_width <= THIN_MAX_N and self.reg_last_dim % 64 == 0:    # every F-ViT config: class-agnostic regression
+            self.fc_reg = LinearThin(self.reg_last_dim, reg_width, ops=ops, fused=fused_reg)
+        else:
+            self.fc_reg = nn.Linear(self.reg_last_dim, reg_width)
         self.init_weights()
 
     def _branch(self, num_convs, num_fcs, in_channels, spatial):

@@ -249,6 +249,11 @@ class _Conv1x1Fn(torch.autograd.Function):
 # against 6.33 ms, 0.95 x when the maps arrive in NCHW; 1.07 x at 1024^2).  Off: fused=True selects the route, as for FUSED_FPN_DEFAULT.
 FUSED_THIN_DEFAULT = False
 THIN_MAX_N = 16                                            # cs_gemm_nt epilogues 10 / 11: one 16-column MFMA tile
+# Whether the thin layers' parameter gradients take epilogue 12 (HipOps.thin_wgrad: dY and X read in place, one launch) where the backend
+# has THIN_WGRAD, instead of dy_rows16 + cast_f32_bf16 + cs_gemm_wgrad_tn + cs_colsum_bf16.  Read when called.  Set from
+# profiles/thin_wgrad_bench.md: on only if the new route is faster at every measured shape with non-overlapping (min .. max) spreads.
+# It is: 4.4 - 5.9 x at rpn640 / rpn1024 (bf16 and fp32 rows) and the mask tail, 2.5 x at fc_reg (4096 x 1024 -> 4).
+THIN_WGRAD_DEFAULT = True
 
 
 def _thin_rows(ops, x):
@@ -287,10 +292,37 @@ def dy_rows16(ops, grads, M):
     return rows
 
 
-def thin_param_grads(ops, mod, dYr, Xb, widths, need):
-    """[(dW [n_i, Cin, 1, 1] | None, db [n_i] | None)] of the modules whose columns sit in dYr bf16 [M, 16]: one cs_gemm_wgrad_tn at N = 16
-    and one cs_colsum_bf16, sliced per module.  need: [(weight?, bias?)]."""
+def thin_wgrad_direct(ops):
+    """Whether the thin layers' parameter gradients take epilogue 12 of cs_gemm_nt (HipOps.thin_wgrad) on this backend."""
+    return bool(getattr(ops, "THIN_WGRAD", False)) and THIN_WGRAD_DEFAULT
+
+
+def thin_wgrad_buffer(ops, mod, M, N, K):
+    """mod's own grow-only workspace of HipOps.thin_wgrad, as det_layer.wgrad keeps its one."""
+    need = ops.thin_wgrad_workspace(M, N, K)
+    ws = mod.__dict__.get("_thin_wgrad_ws")
+    if ws is None or ws.numel() < need or ws.device != mod.weight.device:
+        ws = mod.__dict__["_thin_wgrad_ws"] = ops.empty((need,), F32)
+    return ws
+
+
+def thin_param_grads(ops, mod, dYr, Xb, widths, need, R=None, dY2=None):
+    """[(dW [n_i, Cin, 1, 1] | None, db [n_i] | None)] of the modules in `widths`.  need: [(weight?, bias?)].
+    R is None (the padded route): the modules' columns sit in dYr bf16 [M, 16] and Xb is bf16: one cs_gemm_wgrad_tn at N = 16 and one
+    cs_colsum_bf16, sliced per module.
+    R given (the direct route, thin_wgrad_direct(ops)): dYr is the fp32 gradient as autograd hands it -- rows [M, N] for R == 0, else the
+    contiguous NCHW planes of the first module with dY2 those of the second -- and Xb the saved rows, fp32 or bf16, read in place: ONE
+    HipOps.thin_wgrad launch gives dW and db of both modules, whichever of them are needed."""
     Cin = Xb.shape[1]
+    if R is not None:
+        M, N = Xb.shape[0], sum(widths)
+        dW, db = ops.empty((N, Cin), F32), ops.empty((N,), F32)
+        ops.thin_wgrad(dYr, Xb, dW, db=db, R=R, dY2=dY2, workspace=thin_wgrad_buffer(ops, mod, M, N, Cin))
+        out, c0 = [], 0
+        for n, (w, b) in zip(widths, need):
+            out.append((dW[c0:c0 + n].reshape(n, Cin, 1, 1) if w else None, db[c0:c0 + n] if b else None))
+            c0 += n
+        return out
     dW = db = None
     if any(w for w, _ in need):
         dW = ops.zeros((THIN_MAX_N, Cin), F32)
@@ -308,8 +340,8 @@ def thin_param_grads(ops, mod, dYr, Xb, widths, need):
 class Conv1x1Thin(_ConvLayer):
     """nn.Conv2d(Cin, Cout, 1) with Cout <= 16 -- its parameters, names, initialisation and state dict -- on the thin streaming kernels
     (epilogues 10 / 11 of cs_gemm_nt) when the tensors live on a backend with THIN_HEADS and Cin % 64 == 0; F.conv2d otherwise.  The RPN's
-    rpn_cls / rpn_reg and the mask head's conv_logits.  The weight gradient is cs_gemm_wgrad_tn on dY rows padded to 16 columns, the bias
-    gradient cs_colsum_bf16: no kernel of their own.
+    rpn_cls / rpn_reg and the mask head's conv_logits.  The weight and bias gradients are epilogue 12 (HipOps.thin_wgrad: dY and X read in
+    place, one launch) where thin_wgrad_direct(ops) holds; otherwise cs_gemm_wgrad_tn on dY rows padded to 16 columns and cs_colsum_bf16.
 
     fused: True = the kernels or NotImplementedError, False = F.conv2d, None = FUSED_THIN_DEFAULT where the kernels can run.
     forward(x): x [N, Cin, H, W] fp32 or bf16 of any strides (a channel-last map is read in place) -> contiguous NCHW fp32
@@ -400,6 +432,11 @@ class _ThinFn(torch.autograd.Function):
         out = [None] * (2 * len(convs))
         if any(w or b for w, b in need):
             (X,) = ctx.saved_tensors
+            if thin_wgrad_direct(ops):                                 # the planes as they are, X as it was saved: one launch
+                res = thin_param_grads(ops, convs[0], grads[0], X, widths, need, R=R, dY2=grads[1] if len(grads) == 2 else None)
+                for i, (dw, db) in enumerate(res):
+                    out[2 * i], out[2 * i + 1] = dw, db
+                return (dx, None, None, *out)
             dYr = dy_rows16(ops, grads, M)
             if X.dtype != BF16 and any(w for w, _ in need):            # an fp32 map read in place: the weight gradient's operand is bf16
                 Xc = X if X.is_contiguous() else X.contiguous()

@@ -748,7 +748,7 @@ static int gemm_nt_split_f32(const void* A, const void* B, float* C, int M, int 
 //      4 f32 atomic accumulate (split-K, C pre-zeroed or accumulating) |
 //      5 patch-embed: out row = row + row/group + 1, += extra[(row%group+1)*ldc + col] |
 //      6 residual with a folded LayerNorm (cs_gemm_nt_ln) | 7 bf16 out = GELU(acc + bias) (exact, erf) | 8 bf16 out = QuickGELU(acc + bias)
-//      9 bf16 out = ReLU(acc + bias) | 10 / 11 the thin forms (N <= 16), forward and input gradient: thin.hip
+//      9 bf16 out = ReLU(acc + bias) | 10 / 11 / 12 the thin forms (N <= 16), forward, input gradient and weight gradient: thin.hip
 // splits: 1, except epilogue 4 (atomic) and epilogues 0 / 9 without a folded LayerNorm, whose split-K goes through fp32 partials in `extra`
 //      (>= splits*M*N floats) and splitk_reduce_act_kernel; <= 0 = chosen here (choose_bf16_splits).
 // flags bit0: 0 = global_load_lds staging, 1 = register staging (debug/fallback A-B switch)
@@ -768,7 +768,7 @@ static int gemm_nt_split_f32(const void* A, const void* B, float* C, int M, int 
 static int gemm_nt_impl(const void* A, const void* B, void* C, const float* bias, const float* extra, const float* ln_mean,
                         const float* ln_rstd, const float* ln_colsum, float* stats_part, void* xb_out, int ldxb, int M, int N, int K, int lda,
                         int ldb, int ldc, int epi, int splits, int group, int flags, hipStream_t stream) {
-    if (epi == EPI_THIN_FWD || epi == EPI_THIN_DGRAD) {    // the thin forms have their own argument rules (thin.hip)
+    if (epi == EPI_THIN_FWD || epi == EPI_THIN_DGRAD || epi == EPI_THIN_WGRAD) {    // the thin forms have their own argument rules (thin.hip)
         CS_CHECK_ARG(!ln_mean && !ln_rstd && !ln_colsum && !stats_part && !xb_out, "cs_gemm_nt_ln: epilogue %d takes no folded LayerNorm", epi);
         return cs_thin_launch(A, B, C, bias, extra, M, N, K, lda, ldb, ldc, epi, splits, group, flags, stream);
     }

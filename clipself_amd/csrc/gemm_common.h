@@ -17,7 +17,7 @@
 
 constexpr int BK = 64;
 enum Epi { EPI_BF16 = 0, EPI_F32 = 1, EPI_RESID_F32 = 2, EPI_SWIGLU_BF16 = 3, EPI_ATOMIC_F32 = 4, EPI_PATCH_F32 = 5, EPI_RESID_LN_F32 = 6,
-           EPI_GELU_BF16 = 7, EPI_QGELU_BF16 = 8, EPI_RELU_BF16 = 9, EPI_THIN_FWD = 10, EPI_THIN_DGRAD = 11 };
+           EPI_GELU_BF16 = 7, EPI_QGELU_BF16 = 8, EPI_RELU_BF16 = 9, EPI_THIN_FWD = 10, EPI_THIN_DGRAD = 11, EPI_THIN_WGRAD = 12 };
 // bf16 output of acc + bias, optionally through an activation: the MLP's of the OpenAI-CLIP ViT (1 exact GELU, 2 QuickGELU) or the ReLU
 // behind the detector's FCs (3); 0 none
 constexpr bool epi_is_bf16(int e) { return e == EPI_BF16 || e == EPI_GELU_BF16 || e == EPI_QGELU_BF16 || e == EPI_RELU_BF16; }
@@ -79,7 +79,7 @@ inline long cs_persistent_cap(int reserve) {
 // (the caller falls back to gemm_persist_kernel), 0 on launch, < 0 on error.
 int cs_gemm_stream_launch(GemmArgs a, int epi, int reserve, hipStream_t stream);
 int cs_gemm_stream_launch_f8(GemmArgs a, int epi, int reserve, hipStream_t stream);
-// thin.hip: epilogues 10 / 11 of cs_gemm_nt (N <= 16: a stream over the rows, not a tiled GEMM), with cs_gemm_nt's own argument list.
+// thin.hip: epilogues 10 / 11 / 12 of cs_gemm_nt (N <= 16: a stream over the rows, not a tiled GEMM), with cs_gemm_nt's own argument list.
 int cs_thin_launch(const void* A, const void* B, void* C, const float* bias, const float* extra, int M, int N, int K, int lda, int ldb, int ldc,
                    int epi, int splits, int group, int flags, hipStream_t stream);
 

@@ -21,6 +21,10 @@ EPI_BF16, EPI_F32, EPI_RESID_F32, EPI_SWIGLU_BF16, EPI_ATOMIC_F32, EPI_PATCH_F32
 EPI_RELU_BF16 = 9                       # bf16 = ReLU(acc + bias): the detector box head's Linear + ReLU (linear.LinearAct)
 EPI_THIN_FWD, EPI_THIN_DGRAD = 10, 11   # the thin forms, N <= 16: 1 x 1 convolutions of the RPN and mask heads and their input gradient (conv.Conv1x1Thin)
 THIN_MAX_N = 16
+EPI_THIN_WGRAD = 12                     # their weight and bias gradient: dW[N, K] = dY^T . X over the rows, db = column sums of dY (HipOps.thin_wgrad)
+# epilogue 12's grid and workspace rule (include/clipself_hip.h), restated by thin_wgrad_workspace: a wave takes 32 rows per step, a workgroup
+# 128, at most 2 workgroups per compute unit; every workgroup leaves one partial of N * K + 16 floats behind the 16 floats of db
+THIN_WGRAD_STEP_ROWS, THIN_WGRAD_WG_ROWS, THIN_WGRAD_BLOCKS_PER_CU, THIN_WGRAD_HEAD = 32, 128, 2, 16
 SPLITK_MAX, SPLITK_MIN_KTILES = 8, 16   # cs_gemm_nt's choice of `splits` for epilogues 0 / 9 (include/clipself_hip.h), restated by gemm_nt_splits
 DX_BF16, DX_F32_ASSIGN, DX_F32_ACCUM = range(3)
 ADAMW_GUARD_HEAD, ADAMW_GUARD_SPAN = 8, 16384
@@ -278,6 +282,7 @@ class HipOps:
     LINEAR_ACT = True                   # gemm_nt(epi=EPI_RELU_BF16, splits=, extra=workspace): Linear + ReLU with deterministic split-K (linear.LinearAct)
     FPN_TOPDOWN = True                  # upsample2x_add / pool2x: the FPN's top-down add and its adjoint on channel-last rows; Conv1x1 on gemm_nt (fpn.FPN)
     THIN_HEADS = True                   # thin_fwd / thin_dgrad: 1 x 1 convolutions with Cout <= 16 as streaming kernels, rows or NCHW planes out (conv.Conv1x1Thin, thin_heads)
+    THIN_WGRAD = True                   # thin_wgrad: weight and bias gradient of the thin forms in one streaming launch, dY fp32 rows / planes and X read in place
     BOX_SCORES = True              # box_scores / roialign_fwd(box_scale=): pixel boxes pooled and scored against class embeddings in one launch (ov_head)
 
     def __init__(self):
@@ -438,14 +443,19 @@ class HipOps:
 
     @staticmethod
     def _thin_form(krows, W, thin, thin2, R, split):
-        """Checks shared by thin_fwd / thin_dgrad -> (M, N, K, the `group`, the stride-or-split argument, flags) of cs_gemm_nt's thin forms
-        (include/clipself_hip.h).  krows: the K-wide rows (X / dX); thin: the N-wide side -- rows [M, N] for R == 0, else the first plane
-        block, contiguous with M * split elements; thin2: the second block (M * (N - split) elements) or None."""
+        """Checks shared by thin_fwd / thin_dgrad / thin_wgrad -> (M, N, K, the `group`, the stride-or-split argument, flags) of cs_gemm_nt's
+        thin forms (include/clipself_hip.h).  krows: the K-wide rows (X / dX); W: the bf16 weights [N, K], or the int N where the form has
+        none (thin_wgrad); thin: the N-wide side -- rows [M, N] for R == 0, else the first plane block, contiguous with M * split elements;
+        thin2: the second block (M * (N - split) elements) or None."""
         assert krows.dim() == 2 and krows.stride(1) == 1 and krows.dtype in (torch.float32, torch.bfloat16)
-        assert W.dim() == 2 and W.stride(1) == 1 and W.dtype == torch.bfloat16 and thin.dtype == torch.float32
+        assert thin.dtype == torch.float32
         M, K = krows.shape
-        N = W.shape[0]
-        assert W.shape[1] == K and 1 <= N <= THIN_MAX_N and K % 64 == 0 and M >= 1 and krows.stride(0) >= K
+        if isinstance(W, int):
+            N = W
+        else:
+            assert W.dim() == 2 and W.stride(1) == 1 and W.dtype == torch.bfloat16 and W.shape[1] == K
+            N = W.shape[0]
+        assert 1 <= N <= THIN_MAX_N and K % 64 == 0 and M >= 1 and krows.stride(0) >= K
         flags = 1 if krows.dtype == torch.float32 else 0
         if R == 0:
             assert split is None and thin2 is None, "rows form: one [M, N] tensor, no split"
@@ -489,6 +499,39 @@ class HipOps:
                 "the gate is bf16 rows [M, K] with dX's row stride"
         self._ok(self.lib.cs_gemm_nt(_p(dY), _p(W), _p(dX), _p(dY2), _p(gate), M, N, K, lda, W.stride(0), dX.stride(0), EPI_THIN_DGRAD, 1, group,
                                      flags, self._stream()), "cs_gemm_nt")
+
+    def thin_wgrad_partials(self, M) -> int:
+        """Workgroups along the rows of epilogue 12 (each leaves one partial): min(ceil(M / 128), 2 * compute units)."""
+        return min((M + THIN_WGRAD_WG_ROWS - 1) // THIN_WGRAD_WG_ROWS, THIN_WGRAD_BLOCKS_PER_CU * self.num_cus)
+
+    def thin_wgrad_workspace(self, M, N, K) -> int:
+        """Floats of epilogue 12's workspace (the rule of include/clipself_hip.h): 16 + P * (N * K + 16), P = thin_wgrad_partials(M)."""
+        return THIN_WGRAD_HEAD + self.thin_wgrad_partials(M) * (N * K + THIN_WGRAD_HEAD)
+
+    def thin_wgrad(self, dY, X, dW, db=None, R=0, dY2=None, workspace=None):
+        """Epilogue 12: dW[n, k] = sum_m bf16(dY[m, n]) * bf16(X[m, k]) (overwritten, fp32 [N, K], row stride >= K) and db[n] = sum_m
+        bf16(dY[m, n]).  dY fp32 as in thin_dgrad: rows [M, N] (R == 0) or contiguous planes [M / R, s, R] with the second block dY2.  X bf16
+        / fp32 rows [M, K], read in place.  workspace: fp32, contiguous, at least thin_wgrad_workspace(M, N, K) floats (allocated when None;
+        ValueError when too small); on return workspace[:N] holds db, which is copied into `db` when one is given.  -> the workspace."""
+        self._chk(dY, X, dW, db, dY2, workspace)
+        M, K = X.shape
+        N = dY.shape[1] if R == 0 else (dY.numel() + (0 if dY2 is None else dY2.numel())) // M
+        assert dW.dim() == 2 and dW.dtype == torch.float32 and dW.stride(1) == 1 and dW.shape[1] >= K and dW.shape[0] >= N, \
+            "dW is fp32 [>= N, >= K] with unit column stride"
+        split = None if R == 0 else dY.numel() // M
+        M, N, K, group, lda, flags = self._thin_form(X, int(N), dY, dY2, R, split)
+        need = self.thin_wgrad_workspace(M, N, K)
+        if workspace is None:
+            workspace = self.empty((need,), torch.float32)
+        elif workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() < need:
+            raise ValueError(f"thin_wgrad: M={M}, N={N}, K={K} needs a contiguous fp32 workspace of {need} floats, got {workspace.dtype} with "
+                             f"{workspace.numel()} elements")
+        self._ok(self.lib.cs_gemm_nt(_p(dY), _p(X), _p(dW), _p(dY2), _p(workspace), M, N, K, lda, X.stride(0), dW.stride(0), EPI_THIN_WGRAD, 1,
+                                     group, flags, self._stream()), "cs_gemm_nt")
+        if db is not None:
+            assert db.dtype == torch.float32 and db.numel() == N
+            db.view(-1).copy_(workspace[:N])
+        return workspace
 
     def gemm_nt_splits(self, M, N, K) -> int:
         """The slice count cs_gemm_nt chooses for splits <= 0 on epilogues 0 / 9 (the rule of include/clipself_hip.h): what a caller sizes the

@@ -178,3 +178,101 @@ class _LinearActFn(torch.autograd.Function):
             db = ops.zeros((out,), F32)
             ops.colsum_bf16(dZ, db)
         return dx, dw, db, None, None
+
+
+# ------------------------------------------------------------------------------------------------ thin Linear (the box head's fc_reg)
+THIN_MAX_N = 16                                            # cs_gemm_nt epilogues 10 / 11 / 12: one 16-column MFMA tile
+
+
+class LinearThin(KernelLayer, nn.Linear):
+    """nn.Linear(in_features, out_features) with out_features <= 16 -- its parameters, names, initialisation and state dict -- on the thin
+    streaming kernels (the ROWS forms of epilogues 10 / 11 / 12 of cs_gemm_nt) when the tensors live on a backend with THIN_HEADS and
+    in_features % 64 == 0; F.linear otherwise.  The box head's fc_reg (512 | 1024 -> 4), which LinearAct (out % 8 == 0) does not take.
+
+    fused: True = the kernels or NotImplementedError, False = F.linear, None = conv.FUSED_THIN_DEFAULT where the kernels can run.
+    forward(x): x [..., in_features] fp32 or bf16, read in place where its rows are 16-byte aligned -> **fp32** [..., out_features] on the
+    kernel route WHATEVER x's dtype (acc + bias, not rounded again): what det_losses.bbox_head_loss and det_post.delta2bbox take without
+    a copy.  The input gradient comes back in x's dtype; the parameter gradients are fp32, from HipOps.thin_wgrad where the backend has
+    THIN_WGRAD (and conv.THIN_WGRAD_DEFAULT), from the padded route of conv.thin_param_grads otherwise."""
+    FLAG = "THIN_HEADS"
+    COVERAGE = "in % 64 == 0, out <= 16, fp32 parameters, fp32 / bf16 input"
+
+    def __init__(self, in_features, out_features, bias=True, ops=None, fused=None, **kw):
+        super().__init__(in_features, out_features, bias=bias, **kw)
+        self.ops = ops
+        self.fused = fused
+
+    def covered(self, x) -> bool:
+        return (self.in_features % 64 == 0 and self.out_features <= THIN_MAX_N and self.weight.dtype == F32 and x.dtype in (F32, BF16)
+                and x.dim() >= 1 and x.shape[-1] == self.in_features and x.numel() > 0 and x.device == self.weight.device)
+
+    def describe(self):
+        return f"LinearThin({self.in_features}, {self.out_features})"
+
+    def fused_default(self):
+        from . import conv
+        return conv.FUSED_THIN_DEFAULT
+
+    def forward(self, x):
+        k = self.kernel_backend(x)
+        if k is None:
+            return F.linear(x, self.weight, self.bias)
+        return _LinearThinFn.apply(x, self.weight, self.bias, self, k)
+
+    def gemm_weights(self):
+        """(W bf16 [out, in], bias fp32 [out] | None), rebuilt when the parameters' version counters (or their storage) change."""
+        return packed(self, lambda: (self.weight.detach().to(BF16).contiguous(), bias_f32(self.bias)))
+
+
+def _thin_rows2d(ops, x, width):
+    """x [..., width] fp32 / bf16 -> rows [rows, width] for the thin forms: x itself where its rows are dense enough to be read in place
+    (unit column stride, 16-byte aligned rows and base), a contiguous copy otherwise."""
+    X = x.reshape(-1, width)
+    unit = 4 if X.dtype == F32 else 8
+    if X.stride(1) != 1 or (X.shape[0] > 1 and (X.stride(0) < width or X.stride(0) % unit)) or X.data_ptr() % 16:
+        X = X.contiguous()
+    return X.detach()
+
+
+class _LinearThinFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, ops):
+        inf, out = mod.in_features, mod.out_features
+        W, b32 = mod.gemm_weights()
+        X = _thin_rows2d(ops, x, inf)
+        Y = ops.empty((X.shape[0], out), F32)
+        ops.thin_fwd(X, W, b32, Y, R=0)
+        ctx.mod, ctx.ops, ctx.x_shape, ctx.x_dtype, ctx.has_bias = mod, ops, tuple(x.shape), x.dtype, bias is not None
+        if any(ctx.needs_input_grad[1:3]):
+            ctx.save_for_backward(X)
+        return Y.view(*x.shape[:-1], out)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from .conv import thin_param_grads, thin_wgrad_direct          # conv imports nothing from here
+        mod, ops = ctx.mod, ctx.ops
+        inf, out = mod.in_features, mod.out_features
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+        dY = d_out.reshape(-1, out).to(F32).contiguous()
+        rows = dY.shape[0]
+        dx = dw = db = None
+        if need_x:
+            W, _ = mod.gemm_weights()
+            dX = ops.empty((rows, inf), ctx.x_dtype)
+            ops.thin_dgrad(dY, W, dX, R=0)
+            dx = dX.view(ctx.x_shape)
+        if need_w or need_b:
+            (X,) = ctx.saved_tensors
+            if thin_wgrad_direct(ops):
+                ((dw, db),) = thin_param_grads(ops, mod, dY, X, [out], [(need_w, need_b)], R=0)
+            else:                                                      # the padded route: bf16 dY rows [rows, 16], bf16 X
+                dYr = ops.zeros((rows, THIN_MAX_N), BF16)
+                dYr[:, :out] = dY
+                Xb = X
+                if X.dtype != BF16 and need_w:
+                    Xb = ops.empty((rows, inf), BF16)
+                    ops.cast_f32_bf16(X if X.is_contiguous() else X.contiguous(), Xb)
+                ((dw, db),) = thin_param_grads(ops, mod, dYr, Xb, [out], [(need_w, need_b)])
+            if dw is not None:
+                dw = dw.reshape(out, inf)
+        return dx, dw, db, None, None

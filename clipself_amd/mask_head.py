@@ -11,7 +11,8 @@ laying the [K, C, 28, 28] map out:
     2. that buffer as rows [4*K*196, C] through HipOps.thin_fwd (rows form, N = 1 | num_classes <= 16): the logits, 4 bytes per pixel;
     3. a torch permutation of the [K, 14, 14, 2, 2, N] logits to [K, N, 28, 28].
 The backward is the inverse permutation, HipOps.thin_dgrad with the saved activation as the ReLU's gate, the deconvolution's own
-pieces (det_layer.wgrad, colsum_bf16, gemm_nt with Wg^T) on those rows, and conv_logits' gradients as in conv.Conv1x1Thin.
+pieces (det_layer.wgrad, colsum_bf16, gemm_nt with Wg^T) on those rows, and conv_logits' gradients as in conv.Conv1x1Thin: the rows form
+of HipOps.thin_wgrad on the fp32 dL and the saved activation where conv.thin_wgrad_direct holds, the padded bf16 rows otherwise.
 
 The initialisation follows mmdet's FCNMaskHead.init_weights (Kaiming normal, mode='fan_out', nonlinearity='relu', zero biases for
 `upsample` and `conv_logits`).  mmdet is not installed beside this project, so that part is cited, not run: parity-unpinned.
@@ -22,7 +23,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .conv import THIN_MAX_N, Conv1x1, Conv1x1Thin, thin_param_grads
+from .conv import THIN_MAX_N, Conv1x1, Conv1x1Thin, thin_param_grads, thin_wgrad_direct
 from .det_layer import BF16, EPI_RELU_BF16, F32, epi_for, row_chunks, rows_bf16, rows_to_map, uncovered, wgrad
 from .neck import Deconv2x2
 from .norm_act import ConvModule, apply_norm_cfg
@@ -133,7 +134,9 @@ class _MaskTailFn(torch.autograd.Function):
         dL = d_out.to(F32).reshape(K, Nl, h, 2, w, 2).permute(0, 2, 4, 3, 5, 1).reshape(4 * M, Nl).contiguous()
         A4 = act.view(4 * M, Cout)
         dx = duw = dub = dlw = dlb = None
-        if need_lw or need_lb:
+        if (need_lw or need_lb) and thin_wgrad_direct(ops):                  # the rows form of epilogue 12: dL and the activation in place
+            ((dlw, dlb),) = thin_param_grads(ops, lg, dL, A4, [Nl], [(need_lw, need_lb)], R=0)
+        elif need_lw or need_lb:
             dLr = ops.zeros((4 * M, THIN_MAX_N), BF16)
             dLr[:, :Nl] = dL
             ((dlw, dlb),) = thin_param_grads(ops, lg, dLr, A4, [Nl], [(need_lw, need_lb)])

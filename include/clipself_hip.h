@@ -34,8 +34,8 @@ const char* cs_last_error(void);
  *        (src/open_clip/transformer.py:209-213 `mlp`, :31-34 `QuickGELU`) |
  *      9 bf16 = ReLU(acc+bias), v < 0 ? 0 : v (a NaN passes): the detector box head's Linear + ReLU
  *        (F-ViT/models/fvit_head.py:82-83, 95-96, 104-105: shared_fcs, cls_fcs, reg_fcs)
- *      10 / 11 the THIN forms: 1 <= N <= 16 output columns, a stream over the rows and not a tiled GEMM (see below; their own argument
- *        rules replace the ones of this paragraph)
+ *      10 / 11 / 12 the THIN forms: 1 <= N <= 16 output columns, a stream over the rows and not a tiled GEMM (see below; their own
+ *        argument rules replace the ones of this paragraph); 12 is their weight and bias gradient
  * splits: 1 everywhere except
  *      epi 4: the atomic split-K above;
  *      epi 0 / 9: deterministic split-K for skinny, deep problems (the box head's 4096 x 512 outputs behind K = 12 544).  `splits` > 1, or
@@ -79,7 +79,29 @@ const char* cs_last_error(void);
  *   stay in registers for the whole launch when K == 256) and the grid is min(ceil(M / 64), 8 * compute units) workgroups of 256 threads
  *   with a grid-stride loop: a function of the arguments and the device alone.  Equal inputs give equal bits.
  *   Errors (-1, cs_last_error, nothing launched): N > 16, K % 64 != 0, M % R != 0, s outside [1, N], a stride below its width or one that
- *   breaks the 16-byte rows, misaligned bases, a second block with s == N or none with s < N (epi 11), splits != 1. */
+ *   breaks the 16-byte rows, misaligned bases, a second block with s == N or none with s < N (epi 11), splits != 1.
+ *   epi 12, weight and bias gradient:  dW[n, k] = sum_m bf16(dY[m, n]) * bf16(X[m, k]),  db[n] = sum_m bf16(dY[m, n]),  n < N, k < K.
+ *       The contraction is the M rows.  Both operands are bf16 (dY and fp32 X are rounded to nearest even in registers, so the bits equal
+ *       those of cs_cast_f32_bf16 followed by the bf16 form), the accumulation is fp32 in a fixed order.
+ *       A = dY, fp32, exactly as in epi 11: rows form T = A with ld = lda >= N; planes form P1 = A, P2 = bias (NULL requires s == N) and
+ *       lda = s.  B = X rows [M, K], bf16 or fp32 (flags bit 0), row stride ldb >= K with 16-byte aligned rows and base.
+ *       C = dW fp32 [N, K], row stride ldc >= K (ldc % 4 == 0, 16-byte aligned): OVERWRITTEN, not accumulated; rows >= N and columns >= K
+ *       of a padded buffer are never touched.
+ *       extra = fp32 WORKSPACE, 16-byte aligned, of at least
+ *           16 + P * (N * K + 16) floats,   P = min(ceil(M / 128), 2 * compute units)     (cs_num_compute_units)
+ *       On return extra[0 .. N) holds db and extra[N .. 16) zeros; behind them sit the P per-workgroup partials ([N, K] + 16 floats
+ *       each).  The workspace need not be zeroed: every element that is read was written by the same call.
+ *       A wave owns 32 rows at a time (staged as bf16 in LDS, read back transposed by ds_read_b64_tr_b16 as the B operand of
+ *       v_mfma_f32_16x16x32_bf16, dY^T being the A operand); workgroup b of the P x (K / KC) grid (KC = 256 where K % 256 == 0, else 64;
+ *       256 threads) takes the 128-row blocks b, b + P, b + 2 P, ... of column chunk blockIdx.y, adds its four waves' register partials in
+ *       wave order through LDS and writes partial b.  A second launch adds the partials: 16 contiguous groups of ceil(P / 16) partials
+ *       each in ascending order, then the 16 group sums in ascending order.  With P == 1 the first launch writes dW and db directly.
+ *       Rows of the last, ragged 32-row step that lie past M are loaded from row M - 1 and enter as zeros.  Planes are read 32 bytes
+ *       (eight pixels) at a time where R % 8 == 0 and both blocks are 16-byte aligned, one element at a time otherwise (any R >= 1).
+ *       No atomics; equal inputs give equal bits; 64-bit offsets; nothing outside the stated extents is read or written.
+ *       Errors (-1, nothing launched): those of epi 11 with the roles above, a stride below its width or off the 16-byte rows,
+ *       misaligned X / dW / workspace, splits != 1.  extra == NULL is refused before anything else, in the words the library used for
+ *       code 12 before this form existed ("unknown epilogue 12 ..."): the form exists only with a workspace. */
 int cs_gemm_nt(const void* A, const void* B, void* C, const float* bias, const float* extra, int M, int N, int K,
                int lda, int ldb, int ldc, int epi, int splits, int group, int flags, cs_stream_t stream);
 

@@ -167,11 +167,55 @@ def kernels_alone(ops, M, N, R, split, iters, windows, gate):
     return rows
 
 
+def wgrad_alone(ops, conv_mod, name, M, N, K, geom, split, dt, iters, windows):
+    """Parameter gradients alone at M rows: epilogue 12 (HipOps.thin_wgrad, dY and X read in place) against the route it replaces --
+    dy_rows16 / a padded bf16 copy of dY [+ cast_f32_bf16] + cs_gemm_wgrad_tn at N = 16 + cs_colsum_bf16 (conv.thin_param_grads with
+    R=None, whatever conv.THIN_WGRAD_DEFAULT says).  geom = (B, H, W) for the planes form, None for rows.  -> a table row."""
+    from clipself_amd.conv import Conv1x1Thin
+    holder = Conv1x1Thin(K, N, ops=ops, fused=True).cuda()
+    X = torch.randn(M, K, device="cuda").to(dt)
+    dW, db = torch.empty(N, K, device="cuda"), torch.empty(N, device="cuda")
+    ws = ops.empty((ops.thin_wgrad_workspace(M, N, K),), F32)
+    if geom is not None:
+        Bn, H, Wd = geom
+        widths = [split, N - split]
+        grads = [torch.randn(Bn, n, H, Wd, device="cuda") for n in widths]
+        new = lambda: ops.thin_wgrad(grads[0], X, dW, db=db, R=H * Wd, dY2=grads[1], workspace=ws)
+
+        def old():
+            dYr = conv_mod.dy_rows16(ops, grads, M)
+            Xb = X
+            if dt != BF16:
+                Xb = ops.empty((M, K), BF16)
+                ops.cast_f32_bf16(X, Xb)
+            conv_mod.thin_param_grads(ops, holder, dYr, Xb, widths, [(True, True)] * 2)
+    else:
+        dL = torch.randn(M, N, device="cuda")
+        new = lambda: ops.thin_wgrad(dL, X, dW, db=db, R=0, workspace=ws)
+
+        def old():
+            dYr = ops.zeros((M, 16), BF16)
+            dYr[:, :N] = dL
+            Xb = X
+            if dt != BF16:
+                Xb = ops.empty((M, K), BF16)
+                ops.cast_f32_bf16(X, Xb)
+            conv_mod.thin_param_grads(ops, holder, dYr, Xb, [N], [(True, True)])
+    t = measure({"new": new, "old": old}, iters, windows)
+    must = M * K * (2 if dt == BF16 else 4) + M * N * 4
+    un, uo = statistics.median(t["new"]), statistics.median(t["old"])
+    faster = max(t["new"]) < min(t["old"])
+    return (f"{name}: M = {M}, N = {N}, K = {K}, {'planes' if geom else 'rows'}, {str(dt).split('.')[-1]} X", fmt(t["new"]), fmt(t["old"]), must / 1e6,
+            must / un / 1e6 / STREAM_TBS * 100, uo / un, faster)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--only", default="", help="comma-separated subset of: kernels, rpn640, rpn1024, head640, head1024, mask")
+    ap.add_argument("--only", default="", help="comma-separated subset of: kernels, wgrad, fcreg, rpn640, rpn1024, head640, head1024, mask")
+    ap.add_argument("--route", choices=["default", "new", "old"], default="default",
+                    help="parameter gradients of the module tables: conv.THIN_WGRAD_DEFAULT as it is, forced on (epilogue 12) or off (the padded route)")
     args = ap.parse_args()
     only = set(filter(None, args.only.split(",")))
     want = lambda k: not only or k in only
@@ -181,8 +225,51 @@ def main():
     from clipself_amd.mask_head import FCNMaskHead
     from clipself_amd.rpn_head import RPNHead
     ops = HipOps()
-    print(f"# thin heads on {torch.cuda.get_device_name(0)}: {args.windows} windows of {args.iters} calls, variants alternated in one process")
+    if args.route != "default":
+        conv_mod.THIN_WGRAD_DEFAULT = args.route == "new"
+    print(f"# thin heads on {torch.cuda.get_device_name(0)}: {args.windows} windows of {args.iters} calls, variants alternated in one process; "
+          f"parameter gradients of the modules: {'epilogue 12' if conv_mod.thin_wgrad_direct(ops) else 'the padded route'}")
     wins = []
+
+    if want("wgrad"):
+        rows = []
+        for side in (160, 256):
+            for dt in (BF16, F32):
+                rows.append(wgrad_alone(ops, conv_mod, f"rpn{side * 4}", B * side * side, 15, C, (B, side, side), 3, dt, args.iters, args.windows))
+        rows.append(wgrad_alone(ops, conv_mod, "mask tail", 4 * 1024 * 196, 1, C, None, 1, BF16, args.iters, args.windows))
+        rows.append(wgrad_alone(ops, conv_mod, "fc_reg", 4096, 4, 1024, None, 4, BF16, args.iters, args.windows))
+        print(f"\n## Parameter gradients alone: epilogue 12 against the padded route ({STREAM_TBS} TB/s stream figure)\n\n| shape | new µs median "
+              "(min .. max) | old µs median (min .. max) | MB it must move (X + dY) | new: % of the stream figure | old / new | spreads apart |"
+              "\n|---|---|---|---|---|---|---|")
+        for name, tn, to, mb, pct, ratio, faster in rows:
+            print(f"| {name} | {tn} | {to} | {mb:.1f} | {pct:.0f} | {ratio:.2f} x | {'yes' if faster else 'NO'} |")
+        print(f"\nTHIN_WGRAD_DEFAULT by the rule (faster at every shape, spreads apart): {all(r[-1] for r in rows)}; "
+              f"it is {conv_mod.THIN_WGRAD_DEFAULT} in clipself_amd/conv.py" + ("" if args.route == "default" else f" (forced {args.route} for this run)"))
+
+    if want("fcreg"):
+        from clipself_amd.bbox_head import ConvFCBBoxHead
+        cfg = dict(in_channels=256, fc_out_channels=512, roi_feat_size=7, num_classes=1203, reg_class_agnostic=True,
+                   norm_cfg=dict(type="SyncBN"), num_shared_convs=4, num_shared_fcs=2, num_cls_fcs=1, num_reg_fcs=1)
+        torch.manual_seed(0)
+        heads = {"all kernels, fused_reg=True (fc_reg on LinearThin)": ConvFCBBoxHead(ops=ops, fused=True, fused_reg=True, **cfg).cuda(),
+                 "all kernels, fused_reg=False (fc_reg on F.linear)": ConvFCBBoxHead(ops=ops, fused=True, fused_reg=False, **cfg).cuda()}
+        x = torch.randn(4096, 256, 7, 7, generator=torch.Generator().manual_seed(1)).cuda().contiguous(memory_format=torch.channels_last)
+        xg = x.clone().requires_grad_(True)
+
+        def head_step(h):
+            def run():
+                xg.grad = None
+                for p in h.parameters():
+                    p.grad = None
+                x_cls, bbox_pred = h(xg)
+                (x_cls.sum() + bbox_pred.sum()).backward()
+            return run
+        t = measure({k: head_step(h) for k, h in heads.items()}, max(2, args.iters // 3), args.windows)
+        print("\n## ConvFCBBoxHead forward + backward, 8 x 512 RoIs [4096, 256, 7, 7] fp32 channel-last\n\n| variant | µs median (min .. max) |\n|---|---|")
+        for k, v in t.items():
+            print(f"| {k} | {fmt(v)} |")
+        del heads, x, xg
+        torch.cuda.empty_cache()
 
     if want("kernels"):
         rows = []
