@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .det_layer import (BF16, F32, KernelLayer, bias_f32, conv_covered, epi_for, is_channel_last, kernel_grad, packed, pad_cols, params_key,
+from .det_layer import (BF16, F32, KernelLayer, bias_f32, conv_covered, epi_for, is_channel_last, kernel_grad, packed, pad_cols, param_steps, params_key,
                         row_chunks, rows_bf16, rows_to_map, wgrad)
 
 # Whether fused=None takes the kernels where the backend has them: set from profiles/conv3x3_bench.md by the rule of FUSED_SCORES_DEFAULT
@@ -274,7 +274,8 @@ def _thin_packed(convs):
         if all(c.bias is None for c in convs):
             return Wp, None
         return Wp, torch.cat([c.weight.new_zeros(c.out_channels) if c.bias is None else c.bias.detach() for c in convs]).to(F32).contiguous()
-    return packed(convs[0], build, key=tuple((id(c), *params_key(c.weight, c.bias)) for c in convs), slot="_thin_cache")
+    return packed(convs[0], build, key=tuple((id(c), *params_key(c.weight, c.bias), param_steps(c.weight), param_steps(c.bias)) for c in convs),
+                  slot="_thin_cache")
 
 
 def dy_rows16(ops, grads, M):

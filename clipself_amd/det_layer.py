@@ -4,7 +4,8 @@ helpers that bring maps to channel-last rows and back -- each stated once, for c
   layer_ops     det_backend.kernel_ops plus the one clause the layers need and the functional modules do not: a host backend serves host
                 tensors, which is how the CPU tests run a layer's whole forward and backward on their reference ops;
   KernelLayer   the mixin beside nn.Conv2d / nn.Linear / nn.BatchNorm2d that turns a flag, a default and covered(x) into kernel_backend(x);
-  packed        the packed operands of a module's parameters, rebuilt when a parameter's version counter or storage moves;
+  packed        the packed operands of a module's parameters, rebuilt when a parameter's version counter or storage moves or a torch
+                optimizer that owns it has stepped (the fused ones move neither);
   rows helpers  maps [N, C, H, W] as rows [N*H*W, C] and back, the chunking under CHUNK_BYTES, the padding to the GEMM's K tile, the weight
                 gradient dY^T . X.
 
@@ -14,6 +15,7 @@ constants, signature tables and classes, and load_library() runs when the first 
 from __future__ import annotations
 
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from .det_backend import kernel_ops
 from .hip import EPI_BF16, EPI_F32, EPI_RELU_BF16  # noqa: F401  (EPI_RELU_BF16 for linear and mask_head)
@@ -87,11 +89,32 @@ def params_key(weight, bias):
     return (weight.data_ptr(), version(weight), weight.device, None if bias is None else (bias.data_ptr(), version(bias)))
 
 
+def _optimizer_stepped(optimizer, args, kwargs):
+    for group in optimizer.param_groups:
+        for p in group["params"]:
+            p.__dict__["_cs_steps"] = p.__dict__.get("_cs_steps", 0) + 1
+
+
+register_optimizer_step_post_hook(_optimizer_stepped)      # every torch.optim.Optimizer of the process, whenever it was built
+
+
+def param_steps(t):
+    """How many steps torch optimizers that own tensor t have taken (0 for None, a buffer, a frozen module's parameter).  torch's fused
+    optimizers (AdamW / Adam / SGD with fused=True) write the parameters through one multi-tensor kernel that leaves every `_version`
+    and every storage where it was, so params_key alone cannot see their step; a cache of packed parameters keys on this count as well.
+    The count is kept on the parameter itself by a process-wide optimizer-step hook: a step costs one dictionary write per parameter the
+    optimizer owns, and a module that no optimizer owns is never repacked."""
+    return 0 if t is None else t.__dict__.get("_cs_steps", 0)
+
+
 def packed(mod, build, key=None, slot="_wcache"):
     """The tuple build() makes of mod's parameters (under no_grad), kept in mod.__dict__[slot] -- no buffer, no parameter: state_dict() does
-    not see it -- and rebuilt when `key` (default: params_key of mod.weight and mod.bias) has moved."""
+    not see it -- and rebuilt when `key` (default: params_key of mod.weight and mod.bias) has moved or an optimizer that owns mod.weight
+    or mod.bias has stepped since (param_steps: a step that params_key cannot see; after a step it can see the operands are rebuilt
+    anyway).  A caller with a key of its own over other modules' parameters puts their param_steps into it."""
     if key is None:
         key = params_key(mod.weight, mod.bias)
+    key = (key, param_steps(mod.weight), param_steps(getattr(mod, "bias", None)))
     _wcache = mod.__dict__.get(slot)
     if _wcache is None or _wcache[0] != key:
         with torch.no_grad():

@@ -29,6 +29,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .det_layer import param_steps
+
 # What OpenVocabBoxScores(fused=None) chooses on a backend that has the fused path.  Off: at 8 x 1000 boxes on a 64 x 64 map the one-launch
 # route takes 1.29 / 1.49 / 1.46 x the time of the composition (roialign_fwd + torch) at (E, C) = (512, 66) / (512, 1204) / (768, 1204) on the
 # MI355X -- its grouped pooling phase and its logits phase both lose (profiles/ov_scores_bench.md, tools/ov_scores_bench.py).
@@ -124,7 +126,7 @@ class OpenVocabBoxScores(nn.Module):
     def _embed_rows(self):
         """The [C, E] fp32 copy the kernel reads, rebuilt only when all_embeddings / bg_embedding change (or move)."""
         src = (self.all_embeddings,) + ((self.bg_embedding,) if self.learn_bg else ())
-        key = tuple((t.data_ptr(), t._version, t.device) for t in src)
+        key = tuple((t.data_ptr(), t._version, t.device, param_steps(t)) for t in src)     # a fused optimizer moves no version
         if key != self._rows_key:
             with torch.no_grad():
                 self._rows, self._rows_key = self.all_embed.detach().float().t().contiguous(), key

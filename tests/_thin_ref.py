@@ -73,7 +73,7 @@ class RefOpsThin(RefOpsFPN):
         return offs, ~first[0], s
 
     @staticmethod
-    def _check(krows, W, M, N, K, R, s):
+    def _check_thin(krows, W, M, N, K, R, s):
         if N > 16 or N < 1 or K % 64 or K <= 0 or M <= 0:
             raise RuntimeError("cs_gemm_nt (thin): 1 <= N <= 16, K a positive multiple of 64")
         if R < 0 or (R and M % R):
@@ -89,7 +89,7 @@ class RefOpsThin(RefOpsFPN):
         M, K = X.shape
         N = W.shape[0]
         s = N if split is None else int(split)
-        self._check(X, W, M, N, K, R, s)
+        self._check_thin(X, W, M, N, K, R, s)
         assert out.dtype == F32 and (bias is None or (bias.dtype == F32 and bias.numel() == N))
         acc = _np32(X.to(BF)) @ _np32(W).T                               # fp32 rows are rounded to bf16 (RNE) first
         if bias is not None:
@@ -114,11 +114,11 @@ class RefOpsThin(RefOpsFPN):
         if R == 0:
             assert dY2 is None and tuple(dY.shape) == (M, N) and dY.stride(1) == 1
             s = N
-            self._check(dX, W, M, N, K, R, s)
+            self._check_thin(dX, W, M, N, K, R, s)
             dy = _np32(dY)
         else:
             s = dY.numel() // M
-            self._check(dX, W, M, N, K, R, s)
+            self._check_thin(dX, W, M, N, K, R, s)
             assert dY.is_contiguous() and dY.numel() == M * s and (dY2 is None) == (s == N)
             assert dY2 is None or (dY2.dtype == F32 and dY2.is_contiguous() and dY2.numel() == M * (N - s))
             offs, second, s_used = self._plane_offsets(M, N, R, s)

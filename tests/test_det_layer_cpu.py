@@ -142,6 +142,46 @@ def test_packed_returns_the_cached_tuple_until_a_parameter_moves():
     assert len(calls) == 4 and D.packed(mod, build) is D.packed(mod, build) and len(calls) == 5
 
 
+@pytest.mark.parametrize("opt", ["adamw", "adam", "sgd"])
+def test_packed_is_rebuilt_after_a_fused_optimizer_step(opt):
+    """torch's fused optimizers write the parameters through one multi-tensor kernel: the values change, the version counters and the
+    storages do not, so params_key cannot see the step (found by the chain test, tests/test_gpu_det_chain.py (d), where a live assembly
+    went on computing with the operands packed before AdamW(fused=True).step()).  packed keys on the steps of the optimizers that own
+    the module's parameters as well; a module no optimizer owns keeps its operands."""
+    mod, frozen = nn.Linear(4, 3), nn.Linear(4, 3)
+    calls, build = _packer(mod)
+    fcalls, fbuild = _packer(frozen)
+    first, ffirst = D.packed(mod, build), D.packed(frozen, fbuild)
+    for p in mod.parameters():
+        p.grad = torch.ones_like(p)
+    make = {"adamw": torch.optim.AdamW, "adam": torch.optim.Adam, "sgd": torch.optim.SGD}[opt]
+    before, key = mod.weight.detach().clone(), D.params_key(mod.weight, mod.bias)
+    make(mod.parameters(), lr=0.25, fused=True).step()
+    assert not torch.equal(before, mod.weight.detach()) and D.param_steps(mod.weight) == 1 and D.param_steps(mod.bias) == 1
+    assert D.param_steps(frozen.weight) == 0 and D.param_steps(None) == 0
+    second = D.packed(mod, build)
+    assert second is not first and len(calls) == 2
+    assert torch.equal(second[0], mod.weight.detach().to(BF16)) and torch.equal(second[1], mod.bias.detach())
+    assert D.packed(mod, build) is second and len(calls) == 2                     # no step since: the cached tuple
+    assert D.packed(frozen, fbuild) is ffirst and len(fcalls) == 1                # another module's optimizer repacks nothing here
+    other = D.packed(mod, build, key=("pair", *D.params_key(mod.weight, mod.bias)), slot="_pair")
+    make(mod.parameters(), lr=0.25, fused=True).step()
+    assert D.packed(mod, build, key=("pair", *D.params_key(mod.weight, mod.bias)), slot="_pair") is not other      # a caller's own key too
+
+
+def test_thin_heads_repack_after_a_fused_optimizer_step_of_either_module():
+    """conv._thin_packed keys one cache on two modules: a fused step of the second module alone must rebuild it."""
+    from clipself_amd import conv
+    a, b = conv.Conv1x1Thin(64, 3), conv.Conv1x1Thin(64, 12)
+    first = conv._thin_packed((a, b))
+    assert conv._thin_packed((a, b)) is first
+    for p in b.parameters():
+        p.grad = torch.ones_like(p)
+    torch.optim.AdamW(b.parameters(), lr=0.25, fused=True).step()
+    second = conv._thin_packed((a, b))
+    assert second is not first and torch.equal(second[0][3:].float(), b.weight.detach().view(12, 64).to(BF16).float())
+
+
 def test_packed_without_a_bias_and_with_its_own_key_and_slot():
     mod = nn.Linear(4, 3, bias=False)
     calls, build = _packer(mod)
